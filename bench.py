@@ -6,7 +6,19 @@ batch that is already resident in HBM.  Default workload = BASELINE.json configs
 target is quoted on: 1M synthetic 1 kbp pairs at 5 % error, penalties (2,3,1), score + CIGAR.  ONE JSON line on rank 0.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg4x|cfg5] [--pairs P] [--max-error E]
-                  [--mode ranks|library] [--no-cpu-baseline] [--no-host-to-host]
+                  [--mode ranks|library] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-host-to-host] [--no-configs]]
+
+A plain run does what the headline figure needs and nothing else: it generates the seeded pairs, uploads them, runs the W warm-up
+steps and the K timed steps, writes the outputs of the last timed step when --dump-outputs is given, and prints the line (metric,
+value, ms_per_step, stage times, tiers and the roofline of the main launch, which costs no run of its own: it is computed from the
+timed steps' own clocks and the committed PMC summary).  --full adds every other leg described below: the parity sample against
+the checker, the host-to-host and CLI legs, the CPU baseline, the other configurations, the ONT grid points and, for N > 1, the
+in-library sharded call.  --no-cpu-baseline / --no-host-to-host / --no-configs take single legs out of a --full run again.
+
+--dump-outputs DIR writes what a caller of the timed path receives from the last timed step as DIR/<name>.npy (scores.npy,
+cigar_lengths.npy: float64, one value per pair; cigar_sample_index.npy, cigar_sample_text.npy: a fixed, seeded sample of pairs and
+the bytes of their CIGAR strings, one zero-padded float32 row per sampled pair; under 64 MB together).  The pairs are seeded: the
+same arguments give the same inputs, so the files of two builds can be compared value by value.
 
 Multi-GPU.  --mode ranks (default): one rank per GPU under torch.distributed (RCCL carries the barrier and the
 max-over-ranks of the clock only; no data-path collective), every rank aligns its own P pairs: weak scaling.  When
@@ -15,7 +27,7 @@ torch.distributed.run` child, before anything here touches the GPU) and relays t
 --mode library: ONE process times launch_alignments() -- the reference's host-buffer call (tools/aligner.c:450-474) --
 with N*P pairs sharded inside the library over N devices (what a user of the reference API gets).
 
-Besides the contract fields the line carries
+Besides the contract fields the line carries (roofline in every run, the others with --full)
   roofline      the dominant kernel's main launch against the resource that binds it -- vector instruction issue, from the
                 hardware busy counters of the committed PMC pass of the same command -- with the HBM figures (SURVEY.md 8d
                 algorithmic bytes, the bytes the design moves, the bytes the counters saw) as flat hbm_* keys beside it
@@ -396,6 +408,63 @@ def parity_sample(buf, meta, wl, n_pairs, d_scores, ptrs, st, band):
         return {"error": str(ex)}
 
 
+DUMP_ALL_PAIRS = 1_250_000        # --dump-outputs: per-pair values of up to this many pairs are written whole (at most three files of 10 MB)
+DUMP_TEXT_BYTES = 24 << 20        # ... and the sampled CIGAR texts take at most this much
+DUMP_SEED = 20240607
+
+
+def write_outputs(dirname, scores, cigar_len=None, cigar_of=None, rank=0, world=1):
+    """--dump-outputs: the arrays a caller of the timed path holds after the last timed step.  scores / cigar_len: one value per
+    pair (cigar_len: None in score-only mode, -1 for a pair without a CIGAR); cigar_of(i): the CIGAR bytes of pair i.  Per-pair
+    values are written for every pair (beyond DUMP_ALL_PAIRS pairs: for a seeded sample, pair_index.npy beside them), the CIGAR
+    texts for a seeded sample of pairs -- the prefix of one fixed permutation, as long as DUMP_TEXT_BYTES allow."""
+    os.makedirs(dirname, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+    n = len(scores)
+    perm = np.random.default_rng(DUMP_SEED).permutation(n)
+
+    def save(name, arr):
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), arr)
+
+    keep = None
+    if n > DUMP_ALL_PAIRS:
+        keep = np.sort(perm[:DUMP_ALL_PAIRS])
+        save("pair_index", keep.astype(np.float64))
+    pick = (lambda a: a) if keep is None else (lambda a: a[keep])
+    save("scores", pick(np.asarray(scores)).astype(np.float64))
+    if cigar_len is None:
+        return
+    cigar_len = np.asarray(cigar_len, dtype=np.int64)
+    save("cigar_lengths", pick(cigar_len).astype(np.float64))
+    idx = perm[:min(n, 4096)]
+    while len(idx):
+        width = max(1, int(cigar_len[idx].max()))
+        fit = DUMP_TEXT_BYTES // (4 * width)
+        if fit >= len(idx):
+            break
+        idx = idx[:fit]       # (a shorter prefix of the same permutation: its longest CIGAR can only be shorter)
+    idx = np.sort(idx)
+    text = np.zeros((len(idx), max(1, int(cigar_len[idx].max())) if len(idx) else 1), dtype=np.float32)
+    for row, i in enumerate(idx):
+        if cigar_len[i] > 0:
+            text[row, :cigar_len[i]] = np.frombuffer(cigar_of(int(i)), dtype=np.uint8)
+    save("cigar_sample_index", idx.astype(np.float64))
+    save("cigar_sample_text", text)
+
+
+def dump_resident_outputs(dirname, d_scores, ptrs, n_pairs, st, compute_cigar, rank, world):
+    """The outputs of DeviceAligner.align(fetch=False): the score tensor and, with CIGARs, the text / offset / length buffers."""
+    import wfagpu
+    scores = d_scores[:n_pairs].cpu().numpy()
+    if not compute_cigar:
+        return write_outputs(dirname, scores, rank=rank, world=world)
+    off = wfagpu._d2h(ptrs[1], 8 * n_pairs).view(np.uint64)
+    ln = wfagpu._d2h(ptrs[2], 4 * n_pairs).view(np.uint32).astype(np.int64)
+    ln[ln == 0xFFFFFFFF] = -1
+    text = wfagpu._d2h(ptrs[0], int(st.text_bytes))
+    write_outputs(dirname, scores, ln, lambda i: text[int(off[i]):int(off[i]) + int(ln[i])].tobytes(), rank=rank, world=world)
+
+
 def make_pairs(name, n_pairs, seed, world=1):
     """(world: ranks generating at once on this host -- each takes its share of the cores, not 16 threads apiece)"""
     import wfagpu
@@ -412,9 +481,11 @@ def settle(seconds=3.0):
     time.sleep(seconds)
 
 
-def resident_leg(name, n_pairs, max_error, steps, warmup, device, seed, tuning, inherit_budgets, dist=None, use_pmc=True, data=None):
+def resident_leg(name, n_pairs, max_error, steps, warmup, device, seed, tuning, inherit_budgets, dist=None, use_pmc=True, data=None,
+                 parity=True, dump=None):
     """One workload, resident in HBM: W warm-up steps, K timed steps (barrier + device sync on both sides, max over ranks).
-    Returns (record, buf, meta): the measurements of this rank's run (+ the parity sample, taken from the last timed step)."""
+    Returns (record, buf, meta): the measurements of this rank's run (+ with `parity` the parity sample, taken from the last timed
+    step).  dump: (directory, rank, world) -- the outputs of the last timed step go there (--dump-outputs)."""
     import torch
     import shardlib
     import wfagpu
@@ -464,7 +535,9 @@ def resident_leg(name, n_pairs, max_error, steps, warmup, device, seed, tuning, 
                      "pairs_budget_missed": int(st.pairs_budget_missed), "passes": int(st.sub_batches),
                      "arena_gb": round(st.arena_units * 16 / 1e9, 2)},
            "roofline": build_roofline(name, st, main_ms, acc["launches"] / steps, acc["align_ms"] / steps, wl["cigar"], use_pmc),
-           "parity_sample": parity_sample(buf, meta, wl, n_pairs, d_scores, ptrs, st, band)}
+           "parity_sample": parity_sample(buf, meta, wl, n_pairs, d_scores, ptrs, st, band) if parity else None}
+    if dump:
+        dump_resident_outputs(dump[0], d_scores, ptrs, n_pairs, st, wl["cigar"], dump[1], dump[2])
     al.close()
     del batch
     torch.cuda.empty_cache()
@@ -671,10 +744,15 @@ def main():
     ap.add_argument("--pairs", type=int, default=0, help="pairs per GPU per step (default: the workload's)")
     ap.add_argument("--max-error", type=int, default=0)
     ap.add_argument("--mode", default="ranks", choices=["ranks", "library"])
-    ap.add_argument("--h2h-timing", type=int, default=0, help="stage clocks of the host-to-host calls on stderr (1: per call, 2: per batch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-to-host", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the short legs of the other BASELINE configurations and the CLI leg")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: parity sample against the checker, host-to-host and CLI legs, CPU baseline, the other "
+                         "configurations, ONT grid points, and for N > 1 the in-library sharded call")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (scores, CIGAR lengths, a seeded sample of CIGAR strings) as DIR/<name>.npy")
+    ap.add_argument("--h2h-timing", type=int, default=0, help="--full: stage clocks of the host-to-host calls on stderr (1: per call, 2: per batch)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-host-to-host", action="store_true", help="--full without the host-to-host legs")
+    ap.add_argument("--no-configs", action="store_true", help="--full without the short legs of the other BASELINE configurations and the CLI leg")
     ap.add_argument("--ont-banded-only", action="store_true", help="only the ONT-shaped exact-against-banded grid (the reference's published experiment in shape)")
     ap.add_argument("--no-inherit-budgets", action="store_true", help="sample the score budgets again in every step")
     ap.add_argument("--force-band", action="store_true", help="banded workloads: always run the banded kernels (tuning.force_band)")
@@ -734,7 +812,7 @@ def main():
     tuning.update(wl.get("tuning", {}))      # (switches that are part of a workload: cfg5t3)
     data = make_pairs(WORKLOADS[args.workload].get("pairs_like", args.workload), n_pairs, shardlib.shard_seed(1000, rank), world=world)
     pre = {}
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # The legs that measure COLD calls come first, before this process has allocated (and released) anything big:
         # the CLI as a fresh process, then launch_alignments* from this one (see settle()).
         # (the HIP runtime itself is initialised here, as the CLI's device query does before its clock starts: ~60-90 ms)
@@ -767,7 +845,8 @@ def main():
             except Exception as ex:
                 pre["host_to_host"] = {"error": str(ex)}
     rec, buf, meta = resident_leg(args.workload, n_pairs, max_error, steps, args.warmup, local_rank, shardlib.shard_seed(1000, rank), tuning,
-                                  not args.no_inherit_budgets, dist=dist, use_pmc=default_cmd, data=data)
+                                  not args.no_inherit_budgets, dist=dist, use_pmc=default_cmd, data=data, parity=args.full,
+                                  dump=(args.dump_outputs, rank, world) if args.dump_outputs else None)
     elapsed = rec["elapsed"]
     band = wl["band"]
     total_pairs = n_pairs * steps * world
@@ -798,9 +877,10 @@ def main():
             "stage_ms_per_step": rec["stage_ms_per_step"],
             "tiers": rec["tiers"],
             "roofline": rec["roofline"],
-            "parity_sample": rec["parity_sample"],
         }
-    if rank == 0 and world == 1:
+        if args.full:
+            out["parity_sample"] = rec["parity_sample"]
+    if args.full and rank == 0 and world == 1:
         out.update(pre)
         if not args.no_cpu_baseline:
             # ~10-30 s of CPU work: bounded sample of the same workload
@@ -856,7 +936,7 @@ def main():
             if r.returncode != 0 or not lines:
                 return {"error": f"exit code {r.returncode}: {r.stderr[-400:]}"}
             return json.loads(lines[-1])
-        if not args.no_host_to_host:
+        if args.full and not args.no_host_to_host:
             try:
                 leg = shardlib.rank0_exclusive(dist, host_grp, rank, library_leg)
                 if rank == 0:
@@ -929,6 +1009,14 @@ def library_mode(args, wl, n_pairs, max_error, steps):
     for _ in range(steps):
         fn(buf.ctypes.data, buf.nbytes, meta.ctypes.data, res, opt, False)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # (the caller's result records of the last timed call: error = the score, cigar.buffer = the CIGAR string)
+        scores = np.fromiter((res[i].error for i in range(n)), dtype=np.uint32, count=n).view(np.int32)
+        if wl["cigar"]:
+            cigar_of = lambda i: C.string_at(res[i].cigar.buffer)
+            write_outputs(args.dump_outputs, scores, [len(cigar_of(i)) if res[i].cigar.buffer else -1 for i in range(n)], cigar_of)
+        else:
+            write_outputs(args.dump_outputs, scores)
     stages = wfagpu.last_launch_stats()
     per_dev = [{"slot": i, "device": d["devices"], "wall_ms": round(d["total_ms"], 2), "host_threads": d["host_threads"], "lanes": d["lanes"],
                 "batches": d["batches"], "sequences": "packed on the host" if d["host_packed_batches"] == d["batches"] else

@@ -29,6 +29,6 @@ with open('$R/profiles/$TAG/${WL}_pmc_counters.csv','w') as f:
 print(len(rows),'pmc rows')
 PY
 cp $O/stats/*kernel_stats.csv $R/profiles/$TAG/${WL}_kernel_stats.csv 2>/dev/null
-python3 bench.py --workload $WL --no-configs "$@" 2>$O/bench.err | tail -1 > $R/profiles/$TAG/bench_$WL.json
+python3 bench.py --full --workload $WL --no-configs "$@" 2>$O/bench.err | tail -1 > $R/profiles/$TAG/bench_$WL.json
 cp $R/profiles/$TAG/bench_$WL.json $R/profiles/$TAG/${WL}_pmc_counters.csv $R/profiles/$TAG/${WL}_kernel_stats.csv $O/ 2>/dev/null
 cat $R/profiles/$TAG/bench_$WL.json; echo; head -8 $R/profiles/$TAG/${WL}_kernel_stats.csv

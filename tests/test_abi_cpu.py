@@ -38,7 +38,7 @@ def test_library_exports_every_declared_symbol(lib):
         assert hasattr(lib, name), f"{name} not exported"
 
 
-def test_struct_layouts_match_reference_abi():
+def test_struct_layouts_match_reference_abi(tmp_path):
     """SURVEY.md Appendix B (measured on the reference with gcc x86-64)."""
     assert C.sizeof(wfagpu.SeqPair) == 48 and wfagpu.SeqPair.has_N.offset == 40
     assert C.sizeof(wfagpu.Penalties) == 12
@@ -54,7 +54,7 @@ def test_struct_layouts_match_reference_abi():
 int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu\n",sizeof(sequence_pair_t),sizeof(affine_penalties_t),
  sizeof(wfa_backtrace_t),sizeof(alignment_result_t),sizeof(wfa_cigar_t),sizeof(wfa_alignment_result_t),
  sizeof(wfa_alignment_options_t),sizeof(wfagpu_aligner_t));return 0;}'''
-    exe = "/tmp/wfagpu_abi_probe"
+    exe = str(tmp_path / "wfagpu_abi_probe")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe, "-L", os.path.dirname(wfagpu.LIB_PATH)],
                    input=src.encode(), check=True)
     out = subprocess.run([exe], capture_output=True, check=True).stdout.split()
@@ -121,11 +121,11 @@ def test_generator_is_seeded_and_valid():
 
 @pytest.mark.skipif(not os.path.isdir("/root/reference/examples"), reason="reference tree absent")
 @pytest.mark.parametrize("src,cc", [("auto_example.c", "gcc"), ("manual_example.c", "gcc"), ("auto_example.cpp", "g++")])
-def test_reference_examples_compile_unchanged(lib, src, cc):
+def test_reference_examples_compile_unchanged(lib, src, cc, tmp_path):
     """the reference's example programs, read where they lie, compile and link
     against this library with the reference's own include convention (-I lib -I .)."""
     pkg = os.path.dirname(wfagpu.LIB_PATH)
-    exe = f"/tmp/wfagpu_refexample_{src.replace('.', '_')}"
+    exe = str(tmp_path / f"wfagpu_refexample_{src.replace('.', '_')}")
     subprocess.run([cc, f"/root/reference/examples/{src}", "-o", exe, f"-I{pkg}/lib", f"-I{pkg}", f"-L{pkg}",
                     "-lwfagpu", f"-Wl,-rpath,{pkg}"], check=True)
     assert os.path.exists(exe)
@@ -156,7 +156,7 @@ def test_reference_cli_links_against_this_library(lib, tmp_path):
         assert r.returncode != 0 and "No CUDA devices detected" in r.stderr
 
 
-def test_device_header_structs_match_the_python_mirrors():
+def test_device_header_structs_match_the_python_mirrors(tmp_path):
     """include/wfa_gpu_device.h as the C compiler sees it against the ctypes mirrors in bindings/wfagpu.py: a field added on
     one side only would shift everything behind it (tuning switches, launch configuration, stage times, statistics)."""
     src = r'''
@@ -167,7 +167,7 @@ int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n",sizeof(wfagpu_
  offsetof(wfagpu_amd_config_t,tuning),sizeof(wfagpu_amd_launch_config_t),offsetof(wfagpu_amd_launch_config_t,tuning),
  sizeof(wfagpu_amd_launch_stats_t),offsetof(wfagpu_amd_launch_stats_t,devices),sizeof(wfagpu_amd_stats_t),
  offsetof(wfagpu_amd_stats_t,main_launch_ms),sizeof(wfagpu_amd_batch_t));return 0;}'''
-    exe = "/tmp/wfagpu_device_abi_probe"
+    exe = str(tmp_path / "wfagpu_device_abi_probe")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
     out = [int(v) for v in subprocess.run([exe], capture_output=True, check=True).stdout.split()]
     assert out == [C.sizeof(wfagpu.Tuning), C.sizeof(wfagpu.Config), wfagpu.Config.tuning.offset,

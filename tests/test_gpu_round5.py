@@ -131,7 +131,7 @@ def test_bench_harness_runs_as_a_one_rank_rccl_job():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--workload", "cfg2", "--steps", "50", "--warmup", "3",
-                        "--no-cpu-baseline", "--no-host-to-host", "--no-configs"], capture_output=True, text=True, timeout=600, env=env)
+                        "--full", "--no-cpu-baseline", "--no-host-to-host", "--no-configs"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert lines, r.stdout[-2000:]
