@@ -143,7 +143,7 @@ typedef struct {
     int sample_launches;
     unsigned int sample_passes;
     int waves_per_simd_tier0;          /* instantiation the first wavefront launch used (one-wave exact kernels: 8, 7, 6 or 4) */
-    unsigned int pairs_walked_in_kernel; /* pairs of chains whose wavefront kernels walked their alignments back themselves (no wfa_walk_kernel) */
+    unsigned int pairs_walked_in_kernel; /* retained for the layout of this struct, always 0 (the wavefront kernels no longer walk alignments back) */
     unsigned int pairs_trace_split;    /* long alignments whose backtrace was walked by the wave-per-alignment kernel and replayed by
                                           the lane-per-alignment kernel (passes of 8192 and more; tuning.trace_mode 4: any)        */
 } wfagpu_amd_stats_t;

@@ -776,6 +776,45 @@ def test_long_alignments_walked_by_wavefronts_and_replayed_by_lanes():
             al.close()
 
 
+def test_several_alignments_per_wavefront_backtrace(aligner):
+    """wfa_trace_group_kernel<G>: sequences too long to stage 64 pairs per wavefront (1.7 kbp packed: 64 x 217 words > 48 KiB), op lists
+    short (largest score of the pass <= 512), tuning.trace_mode 0 and G * 1024 or more pairs in the pass -- G = 8 from 8192 pairs, 4
+    from 4096, 2 from 2048 (the planner's rule, csrc/trace_layout.h; tests/trace_plan_check.cpp pins these sizes).  What counts is the
+    CHAIN that is traced: a batch of 8192 and more pairs first gives max(512, n / 16) of them to the sample that tunes the score budgets
+    (traced as a chain of their own, one wavefront each), so the largest batch is 8800 pairs: 550 sampled, a chain of 8250.  Resident
+    batches of 2100, 4200 and 8800 pairs, scores and CIGARs byte for byte the checker's; then the largest batch under -B, where the backtrace
+    replaces scores by the cost of the text it emits (WfaTraceParams::score_fix): by policy the exact kernels run (optimal results), with
+    tuning.force_band the band (valid alignments, cost == score >= optimum)."""
+    pen = (2, 3, 1)
+    buf, meta = wfagpu.generate_pairs(8800, 1700, 0.01, seed=1706)
+    pairs = wfagpu.pairs_from_layout(buf, meta)
+    so, co, _ = oracle_lib.oracle_batch(buf, meta, pen, cigar=True, nthreads=16)
+    assert int(so.max()) <= 512
+    assert len(pairs) - max(512, len(pairs) // 16) >= 8 * 1024
+    for n in (2100, 4200, 8800):
+        b, m = (buf, meta) if n == len(pairs) else wfagpu.layout_pairs(pairs[:n])
+        s, c = _run(aligner, b, m, pen, max_error=300)
+        assert np.array_equal(s, so[:n]), n
+        assert c == co[:n], n
+    for force in (False, True):
+        al = wfagpu.DeviceAligner(0, force_band=1 if force else 0)
+        try:
+            batch = al.upload(buf, meta)
+            s, c = al.align(batch, pen, max_error=300, compute_cigar=True, band=25, band_width=128)
+            st = al.stats()
+            if force:
+                assert st.pairs_banded > len(pairs) * 8 // 9
+                assert (s >= so).all()
+                for i in range(0, len(pairs), 9):
+                    ok, cost = oracle_lib.check_cigar(pairs[i][0], pairs[i][1], c[i], pen)
+                    assert ok and cost == s[i]
+            else:
+                assert st.pairs_banded == 0 and st.auto_budget > 0
+                assert np.array_equal(s, so) and c == co
+        finally:
+            al.close()
+
+
 def test_rings_that_fill_lds_to_the_last_bytes():
     """Score budgets swept in small steps across the point where the sixteen-wave ring stops fitting a CU's LDS: every plan on
     either side must launch (a ring within the last 256 bytes of LDS once did not -- a static LDS word had crept into the

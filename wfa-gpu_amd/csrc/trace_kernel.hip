@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "wfa_device.h"
+#include "trace_layout.h"
 
 namespace {
 
@@ -230,6 +231,8 @@ constexpr int TRACE_THREADS = 64;
 // Where the origin bytes of a pair are (wfa_device.h): behind a row table -- [score] = {arena unit of the row, lo} --, or (the one-wave
 // exact tier, round 6) in the pair's block of TILES: a 64-byte header {WFA_ROW_NONE, wlo, tile columns, budget}, then 64-byte tiles of
 // 4 scores x 16 diagonals, tile (s >> 2, (k - wlo) >> 4), byte (s & 3) * 16 + ((k - wlo) & 15).
+// The layouts are told apart HERE and nowhere else, by the first word of the block (WFA_ROW_NONE, wfa_device.h): every ROWS producer
+// writes word 0 of its table, and a row unit can never equal the marker (the arena is capped at WFA_ARENA_MAX_BYTES).
 struct BtBlock { const uint8_t* blk; bool tiled; int wlo; uint32_t cols; };
 __device__ __forceinline__ BtBlock bt_block(const WfaTraceParams& p, const uint32_t pair) {
   BtBlock b;
@@ -242,7 +245,6 @@ __device__ __forceinline__ BtBlock bt_block(const WfaTraceParams& p, const uint3
 // score sr around diagonal k into dst; kbase: the diagonal of dst[0].  Row-table layout: 16 bytes, diagonals k-8 .. k+7 (one unaligned
 // load).  Tiles: the two 16-diagonal tile columns whose 32 diagonals have k at least 8 from either end (two aligned 16-byte loads).
 // Every lane sets the same kbase (it depends on k and the pair only).  Rows of scores < 0 and bytes outside the block read as 0.
-constexpr int TILE_LDS_W = 32;
 __device__ __forceinline__ void fetch_bt_rows(const WfaTraceParams& p, const BtBlock& bb, const int sr, const int k, int& kbase, uint8_t* dst) {
   uint4 v0 = make_uint4(0, 0, 0, 0), v1 = make_uint4(0, 0, 0, 0);
   if (bb.tiled) {
@@ -270,6 +272,40 @@ __device__ __forceinline__ void fetch_bt_rows(const WfaTraceParams& p, const BtB
   reinterpret_cast<uint4*>(dst)[1] = v1;
 }
 
+// One step of the backward walk: the origin byte `code` of cell (s, k) in matrix `state` (0: M, 1: I, 2: D) gives the operation
+// that led there; s, k and state move to the cell it came from.  OP_NONE (nothing moved): the cell is not valid, a broken trace.
+// (Gap open or extension as selects, said explicitly: the compiler made them of the branches the kernels had written out, and does
+// not once the paths of this function meet in its return value -- 3.5 % of the wave kernel's time.)
+constexpr uint32_t OP_NONE = 0;
+__device__ __forceinline__ uint32_t walk_step(const uint32_t code, int& state, int& s, int& k, const WfaTraceParams& p) {
+  uint32_t op;
+  const bool i_ext = (code & BT_I_EXT) != 0, d_ext = (code & BT_D_EXT) != 0;
+  if (state == 0) {
+    const uint32_t org = code & BT_M_MASK;
+    if (org == BT_M_X) { op = OP_X | OP_EXT_AFTER; s -= p.x; }
+    else if (org == BT_M_I) { op = OP_I | OP_EXT_AFTER; --k; s -= i_ext ? p.e : p.oe; state = i_ext ? 1 : 0; }
+    else if (org == BT_M_D) { op = OP_D | OP_EXT_AFTER; ++k; s -= d_ext ? p.e : p.oe; state = d_ext ? 2 : 0; }
+    else return OP_NONE;
+  } else if (state == 1) {
+    op = OP_I; --k; s -= i_ext ? p.e : p.oe; state = i_ext ? 1 : 0;
+  } else {
+    op = OP_D; ++k; s -= d_ext ? p.e : p.oe; state = d_ext ? 2 : 0;
+  }
+  return op;
+}
+// a consistent walk ends in M at (0, 0)
+__device__ __forceinline__ bool walk_ended(const int s, const int state, const int k) { return s == 0 && state == 0 && k == 0; }
+
+// One 64-byte line -> the lane's cache slot in LDS.
+__device__ __forceinline__ void cache_line(const void* line, uint2* const slot) {
+  const uint4* src = reinterpret_cast<const uint4*>(line);
+  const uint4 a = src[0], b = src[1], c = src[2], d = src[3];
+  slot[0] = make_uint2(a.x, a.y); slot[1] = make_uint2(a.z, a.w);
+  slot[2] = make_uint2(b.x, b.y); slot[3] = make_uint2(b.z, b.w);
+  slot[4] = make_uint2(c.x, c.y); slot[5] = make_uint2(c.z, c.w);
+  slot[6] = make_uint2(d.x, d.y); slot[7] = make_uint2(d.z, d.w);
+}
+
 // The backward walk of ONE alignment (one lane): follows the origin bytes from the final cell to (0, 0) and leaves the operations
 // as a byte list that grows downwards from q_end (op number n, 0 = last operation of the alignment, is byte q_end[-1-n]; q_end is
 // 4-byte aligned, four ops go out as one word).  tab_cache: this lane's 8 row-table entries of LDS.  false: broken trace.
@@ -277,83 +313,92 @@ __device__ __forceinline__ bool walk_ops(const WfaTraceParams& p, const uint32_t
                                          uint8_t* const q_end, const uint32_t need_ops, uint2* const tab_cache_lane, uint32_t& nops_out) {
   bool fail = false;
   uint32_t nops = 0, word = 0;
-  {
-    // row table of the pair: [score] = {arena unit of the origin bytes, lo} -- or (the one-wave exact tier, round 6) the pair's block of
-    // TILES: a 64-byte header {WFA_ROW_NONE, wlo, tile columns, budget}, then 64-byte tiles of 4 scores x 16 diagonals, tile
-    // (s >> 2, (k - wlo) >> 4), byte (s & 3) * 16 + ((k - wlo) & 15): no table to consult, and the ~55 origin bytes of a 1 kbp
-    // alignment sit on ~35 cache lines instead of 55 + 19 lines of row table
-    const uint8_t* const blk = p.arena + (size_t)p.bt_final_row[pair] * 16;
-    const uint2* tab = reinterpret_cast<const uint2*>(blk);
-    const uint4 hdr = *reinterpret_cast<const uint4*>(blk);
-    const bool tiled = hdr.x == WFA_ROW_NONE;
-    const int t_wlo = (int)hdr.y; const uint32_t t_cols = hdr.z;
-    int k = tlen - plen, s = score;
-    int state = 0;  // 0: M, 1: I, 2: D
-    int cached = -1;
-    while (s > 0) {
-      if (nops >= need_ops) { fail = true; break; }
-      uint32_t code;
-      if (tiled) {
-        // (the tile is kept in this lane's 64 bytes of LDS -- the row-table cache of the other layout -- until the walk leaves it: a
-        // mismatch at x = 2 stays in its tile every other step)
-        const uint32_t d = (uint32_t)(k - t_wlo);
-        if ((d >> 4) >= t_cols) { fail = true; break; }      // (a broken trace must not leave the block)
-        const int tile_id = (int)(((uint32_t)s >> 2) * t_cols + (d >> 4));
-        if (tile_id != cached) {
-          cached = tile_id;
-          const uint4* src = reinterpret_cast<const uint4*>(blk + 64u + (size_t)tile_id * 64u);
-          const uint4 a = src[0], b = src[1], c2 = src[2], d4 = src[3];
-          tab_cache_lane[0] = make_uint2(a.x, a.y); tab_cache_lane[1] = make_uint2(a.z, a.w);
-          tab_cache_lane[2] = make_uint2(b.x, b.y); tab_cache_lane[3] = make_uint2(b.z, b.w);
-          tab_cache_lane[4] = make_uint2(c2.x, c2.y); tab_cache_lane[5] = make_uint2(c2.z, c2.w);
-          tab_cache_lane[6] = make_uint2(d4.x, d4.y); tab_cache_lane[7] = make_uint2(d4.z, d4.w);
-        }
-        code = reinterpret_cast<const uint8_t*>(tab_cache_lane)[((uint32_t)s & 3u) * 16u + (d & 15u)];
-      } else {
-        if ((s >> 3) != cached) {
-          cached = s >> 3;
-          const uint4* src = reinterpret_cast<const uint4*>(tab + (cached << 3));
-          const uint4 a = src[0], b = src[1], c2 = src[2], d = src[3];
-          tab_cache_lane[0] = make_uint2(a.x, a.y); tab_cache_lane[1] = make_uint2(a.z, a.w);
-          tab_cache_lane[2] = make_uint2(b.x, b.y); tab_cache_lane[3] = make_uint2(b.z, b.w);
-          tab_cache_lane[4] = make_uint2(c2.x, c2.y); tab_cache_lane[5] = make_uint2(c2.z, c2.w);
-          tab_cache_lane[6] = make_uint2(d.x, d.y); tab_cache_lane[7] = make_uint2(d.z, d.w);
-        }
-        const uint2 row = tab_cache_lane[s & 7];
-        code = p.arena[(size_t)row.x * 16 + (uint32_t)(k - (int)row.y)];
-      }
-      uint32_t op;
-      if (state == 0) {
-        const uint32_t org = code & BT_M_MASK;
-        if (org == BT_M_X) { op = OP_X | OP_EXT_AFTER; s -= p.x; }
-        else if (org == BT_M_I) {
-          op = OP_I | OP_EXT_AFTER; --k;
-          if (code & BT_I_EXT) { s -= p.e; state = 1; } else { s -= p.oe; }
-        } else if (org == BT_M_D) {
-          op = OP_D | OP_EXT_AFTER; ++k;
-          if (code & BT_D_EXT) { s -= p.e; state = 2; } else { s -= p.oe; }
-        } else { fail = true; break; }
-      } else if (state == 1) {
-        op = OP_I; --k;
-        if (code & BT_I_EXT) { s -= p.e; } else { s -= p.oe; state = 0; }
-      } else {
-        op = OP_D; ++k;
-        if (code & BT_D_EXT) { s -= p.e; } else { s -= p.oe; state = 0; }
-      }
-      // the list grows downwards from q_end: op number n (0 = last operation of the alignment) is byte q_end[-1-n]
-      word = (word << 8) | op;
-      ++nops;
-      if ((nops & 3u) == 0u) reinterpret_cast<uint32_t*>(q_end)[-(int)(nops >> 2)] = word;
+  // (tiles: no table to consult, and the ~55 origin bytes of a 1 kbp alignment sit on ~35 cache lines instead of 55 + 19 lines of
+  // row table)
+  const BtBlock bb = bt_block(p, pair);
+  const uint2* tab = reinterpret_cast<const uint2*>(bb.blk);
+  int k = tlen - plen, s = score;
+  int state = 0;  // 0: M, 1: I, 2: D
+  int cached = -1;
+  while (s > 0) {
+    if (nops >= need_ops) { fail = true; break; }
+    uint32_t code;
+    if (bb.tiled) {
+      // (the tile is kept in this lane's 64 bytes of LDS -- the row-table cache of the other layout -- until the walk leaves it: a
+      // mismatch at x = 2 stays in its tile every other step)
+      const uint32_t d = (uint32_t)(k - bb.wlo);
+      if ((d >> 4) >= bb.cols) { fail = true; break; }      // (a broken trace must not leave the block)
+      const int tile_id = (int)(((uint32_t)s >> 2) * bb.cols + (d >> 4));
+      if (tile_id != cached) { cached = tile_id; cache_line(bb.blk + 64u + (size_t)tile_id * 64u, tab_cache_lane); }
+      code = reinterpret_cast<const uint8_t*>(tab_cache_lane)[((uint32_t)s & 3u) * 16u + (d & 15u)];
+    } else {
+      if ((s >> 3) != cached) { cached = s >> 3; cache_line(tab + (cached << 3), tab_cache_lane); }
+      const uint2 row = tab_cache_lane[s & 7];
+      code = p.arena[(size_t)row.x * 16 + (uint32_t)(k - (int)row.y)];
     }
-    if (s != 0 || state != 0 || k != 0) fail = true;
-    if (!fail && (nops & 3u)) {
-      // the last, partial word: its ops are the first operations of the alignment
-      uint8_t* qq = q_end - (nops & ~3u);
-      for (int r = (int)(nops & 3u) - 1; r >= 0; --r) *--qq = (uint8_t)(word >> (8 * r));     // (oldest of them first: highest address)
-    }
-    }
+    const uint32_t op = walk_step(code, state, s, k, p);
+    if (op == OP_NONE) { fail = true; break; }
+    // the list grows downwards from q_end: op number n (0 = last operation of the alignment) is byte q_end[-1-n]
+    word = (word << 8) | op;
+    ++nops;
+    if ((nops & 3u) == 0u) reinterpret_cast<uint32_t*>(q_end)[-(int)(nops >> 2)] = word;
+  }
+  if (!walk_ended(s, state, k)) fail = true;
+  if (!fail && (nops & 3u)) {
+    // the last, partial word: its ops are the first operations of the alignment
+    uint8_t* qq = q_end - (nops & ~3u);
+    for (int r = (int)(nops & 3u) - 1; r >= 0; --r) *--qq = (uint8_t)(word >> (8 * r));     // (oldest of them first: highest address)
+  }
   nops_out = nops;
   return !fail;
+}
+
+// What a pair's sequences are to a kernel: lengths, words to stage (trace_seq_words), where the words are.
+struct PairSeqs {
+  int plen, tlen; const uint32_t* P; const uint32_t* T; int raw;
+  __device__ __forceinline__ int pwords() const { return (int)trace_seq_words((unsigned)plen, raw != 0); }
+  __device__ __forceinline__ int twords() const { return (int)trace_seq_words((unsigned)tlen, raw != 0); }
+};
+__device__ __forceinline__ PairSeqs pair_seqs(const WfaTraceParams& p, const size_t pair, const int raw) {
+  const WfaSeqPair mp = p.meta[pair];
+  PairSeqs q;
+  q.plen = (int)mp.pattern_len; q.tlen = (int)mp.text_len;
+  q.P = p.packed + ((raw ? mp.pattern_offset : mp.pattern_offset_packed) >> 2);
+  q.T = p.packed + ((raw ? mp.text_offset : mp.text_offset_packed) >> 2);
+  q.raw = raw;
+  return q;
+}
+
+// lane j's pointer, as a scalar
+__device__ __forceinline__ const uint32_t* readlane_ptr(const uint32_t* ptr, const int j) {
+  return reinterpret_cast<const uint32_t*>(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(reinterpret_cast<unsigned long long>(ptr) >> 32), j) << 32) |
+                                           (uint32_t)__builtin_amdgcn_readlane((int)reinterpret_cast<unsigned long long>(ptr), j));
+}
+
+// p.raw -> the template argument of the replay (the kernels that are not compiled per class)
+template <bool OPS_LDS = false, typename PV, typename TV, typename... A>
+__device__ __forceinline__ uint32_t replay_any(const int raw, const uint8_t* ops, const uint32_t nops, PV& Pw, TV& Tw, A... a) {
+  return raw ? replay_views<true, OPS_LDS>(ops, nops, Pw, Tw, a...) : replay_views<false, OPS_LDS>(ops, nops, Pw, Tw, a...);
+}
+
+// The end of a pair in every kernel that writes texts: where its CIGAR is and how long -- or that it has none.
+__device__ __forceinline__ void finish_pair(const WfaTraceParams& p, const size_t pair, const bool fail, const unsigned long long off = 0,
+                                            const uint32_t len = 0, const int cost = 0, const int score = 0) {
+  if (fail) {
+    p.cigar_off[pair] = 0;
+    p.cigar_len[pair] = 0xFFFFFFFFu;
+    return;
+  }
+  p.cigar_off[pair] = off;
+  p.cigar_len[pair] = len;
+  // The text's own gap-affine cost.  Exact alignments: it equals the wavefront score (checked: a
+  // difference would mean a broken trace).  Adaptive band: a path may open two gaps back to back
+  // where the extension cell had left the band; printed, they are one gap and cost less -- the
+  // reported score follows the alignment that is returned.
+  if (cost != score) {
+    if (p.score_fix) p.score_fix[pair] = cost;
+    else p.cigar_len[pair] = 0xFFFFFFFFu;
+  }
 }
 
 // Phase 1 kernel: backward walk over the origin bytes, one lane per alignment: a chain of dependent HBM reads.  Leaves the op
@@ -364,7 +409,7 @@ __global__ void __launch_bounds__(WALK_WAVES * 64) wfa_walk_kernel(const WfaTrac
   // line survives in L2 until its next use), not by bytes.  Per operation it needs a row-table entry, an origin byte and
   // an op store; two of the three are batched: row-table entries are fetched 8 at a time (one 64-byte line) into this
   // lane's LDS slot, ops are collected four to a register and stored as one word.
-  __shared__ uint2 tab_cache[WALK_WAVES * 64][9];          // [thread][entry & 7] (9: bank spread)
+  __shared__ uint2 tab_cache[WALK_WAVES * 64][LANE_CACHE_BYTES / 8];          // [thread][entry & 7] (9 entries: bank spread)
   __shared__ uint32_t wave_total[WALK_WAVES];
   __shared__ unsigned long long block_base;
   // A grid of two workgroups (eight wavefronts) per CU strides over the list (WfaTraceParams::walk_grid_cap): HBM serves no more
@@ -377,7 +422,6 @@ __global__ void __launch_bounds__(WALK_WAVES * 64) wfa_walk_kernel(const WfaTrac
     uint32_t pair = 0;
     if (active) pair = p.work ? p.work[gid] : gid;
     if (active && p.status[pair] != WFA_ST_DONE) active = false;
-    if (active && p.bt_final_row[pair] == WFA_ROW_NONE) active = false;      // (walked by its wavefront kernel: the op list is in the arena)
     int score = 0, plen = 0, tlen = 0;
     if (active) {
       score = p.score[pair];
@@ -416,20 +460,16 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_win_kernel(const WfaTr
   uint32_t* slot = win_lds + lane * (2 * SeqWindow::WORDS + 1);     // (odd stride: lanes at the same window index hit different banks)
   SeqWindow pv{nullptr, 0, slot, -1000}, tv{nullptr, 0, slot + SeqWindow::WORDS, -1000};
   if (active) {
-    const WfaSeqPair mp = p.meta[pair];
-    plen = (int)mp.pattern_len; tlen = (int)mp.text_len;
-    const int sh = p.raw ? 2 : 4;
-    pv.g = p.packed + ((p.raw ? mp.pattern_offset : mp.pattern_offset_packed) >> 2);
-    tv.g = p.packed + ((p.raw ? mp.text_offset : mp.text_offset_packed) >> 2);
-    pv.nwords = ((plen + (1 << sh) - 1) >> sh) + 1; tv.nwords = ((tlen + (1 << sh) - 1) >> sh) + 1;
-    { const unsigned long long off = p.cigar_off[pair]; q = ((off & WFA_OPS_IN_ARENA) ? p.arena : p.ops) + (off & ~WFA_OPS_IN_ARENA); }
+    const PairSeqs sq = pair_seqs(p, pair, p.raw);
+    plen = sq.plen; tlen = sq.tlen;
+    pv.g = sq.P; tv.g = sq.T; pv.nwords = sq.pwords(); tv.nwords = sq.twords();
+    q = p.ops + p.cigar_off[pair];
     nops = p.cigar_len[pair];
     fail = nops == 0xFFFFFFFFu;
   }
   uint32_t len = 0;
   if (active && !fail) {
-    len = p.raw ? replay_views<true>(q, nops, pv, tv, plen, tlen, nullptr, 0, 0, 0, nullptr)
-                : replay_views<false>(q, nops, pv, tv, plen, tlen, nullptr, 0, 0, 0, nullptr);
+    len = replay_any(p.raw, q, nops, pv, tv, plen, tlen, (char*)nullptr, 0, 0, 0, (int*)nullptr);
     if (len == 0xFFFFFFFFu) fail = true;
   }
   const uint32_t need_txt = (active && !fail) ? len + 1u : 0u;
@@ -439,19 +479,9 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_win_kernel(const WfaTr
     if (!fail) {
       int cost = 0;
       pv.base = -1000; tv.base = -1000;
-      if (p.raw) replay_views<true>(q, nops, pv, tv, plen, tlen, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
-      else replay_views<false>(q, nops, pv, tv, plen, tlen, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
-      p.cigar_off[pair] = txt_off;
-      p.cigar_len[pair] = len;
-      // (the text's own gap-affine cost must equal the score; adaptive band: the score follows the text -- see below)
-      if (cost != p.score[pair]) {
-        if (p.score_fix) p.score_fix[pair] = cost;
-        else p.cigar_len[pair] = 0xFFFFFFFFu;
-      }
-    } else {
-      p.cigar_off[pair] = 0;
-      p.cigar_len[pair] = 0xFFFFFFFFu;
-    }
+      replay_any(p.raw, q, nops, pv, tv, plen, tlen, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
+      finish_pair(p, pair, false, txt_off, len, cost, p.score[pair]);
+    } else finish_pair(p, pair, true);
   }
 }
 
@@ -461,8 +491,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_win_kernel(const WfaTr
 // half of the emit kernel's time).  Pw / Tw come in as the lanes' global addresses and leave as their LDS addresses.
 __device__ __forceinline__ void stage_pairs(const WfaTraceParams& p, const int PPW, const int lane, const bool active, const int plen, const int tlen,
                                             const uint32_t*& Pw, const uint32_t*& Tw, uint32_t* const seq_lds) {
-  const int sh = p.raw ? 2 : 4;
-  const int pw = active ? ((plen + (1 << sh) - 1) >> sh) + 1 : 0, tw = active ? ((tlen + (1 << sh) - 1) >> sh) + 1 : 0;
+  const int pw = active ? (int)trace_seq_words((unsigned)plen, p.raw != 0) : 0, tw = active ? (int)trace_seq_words((unsigned)tlen, p.raw != 0) : 0;
   const int stride = p.seq_lds_stride;   // odd number of words per lane
   constexpr int SG = 8;
   for (int j0 = 0; j0 < PPW; j0 += SG) {      // (PPW is a multiple of SG)
@@ -471,10 +500,7 @@ __device__ __forceinline__ void stage_pairs(const WfaTraceParams& p, const int P
 #pragma unroll
     for (int u = 0; u < SG; ++u) {
       const int j = j0 + u;     // (uniform: the lanes' values come over as scalars)
-      gp[u] = reinterpret_cast<const uint32_t*>(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(reinterpret_cast<unsigned long long>(Pw) >> 32), j) << 32) |
-                                                (uint32_t)__builtin_amdgcn_readlane((int)reinterpret_cast<unsigned long long>(Pw), j));
-      gt[u] = reinterpret_cast<const uint32_t*>(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(reinterpret_cast<unsigned long long>(Tw) >> 32), j) << 32) |
-                                                (uint32_t)__builtin_amdgcn_readlane((int)reinterpret_cast<unsigned long long>(Tw), j));
+      gp[u] = readlane_ptr(Pw, j); gt[u] = readlane_ptr(Tw, j);
       pwj[u] = __builtin_amdgcn_readlane(pw, j); twj[u] = __builtin_amdgcn_readlane(tw, j);
       maxw = max(maxw, max(pwj[u], twj[u]));
     }
@@ -508,10 +534,7 @@ __device__ __forceinline__ void stage_pairs(const WfaTraceParams& p, const int P
 // texts (block_alloc: one returning atomic per workgroup -- the 1563 wavefronts of a 100k-pair launch, all at that point within
 // microseconds of each other, queued ~11 ns each for the one counter: configs[1] with CIGARs, backtrace 0.049 -> 0.037 ms.  The same
 // for wfa_emit_kernel, whose wavefronts come by in rounds, changed nothing: 1M x 1 kbp pairs 3.05 / 3.07 ms.)
-constexpr int LANE_WAVES = 4;
-__host__ __device__ inline size_t lane_kernel_wave_bytes(int emit_pairs, int seq_lds_stride, int ops_lds_bytes) {
-  return ((size_t)emit_pairs * seq_lds_stride * 4 + (size_t)emit_pairs * ops_lds_bytes + (size_t)64 * 9 * 8 + 15) & ~(size_t)15;
-}
+// (LANE_WAVES and the share, lane_kernel_wave_bytes: trace_layout.h)
 template <bool RAW>
 __global__ void __launch_bounds__(LANE_WAVES * 64) wfa_trace_lane_kernel(const WfaTraceParams p) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lane_lds[];
@@ -522,7 +545,7 @@ __global__ void __launch_bounds__(LANE_WAVES * 64) wfa_trace_lane_kernel(const W
   uint32_t* const seq_lds = lane_lds + (size_t)wv * (lane_kernel_wave_bytes(PPW, p.seq_lds_stride, p.ops_lds_bytes) >> 2);
   const uint32_t gid = (blockIdx.x * (uint32_t)LANE_WAVES + (uint32_t)wv) * (uint32_t)PPW + (uint32_t)lane;
   uint8_t* const ops_lds = reinterpret_cast<uint8_t*>(seq_lds + (size_t)PPW * p.seq_lds_stride);
-  uint2* const tab_cache = reinterpret_cast<uint2*>(ops_lds + (size_t)PPW * p.ops_lds_bytes);      // [lane][9]
+  uint2* const tab_cache = reinterpret_cast<uint2*>(ops_lds + (size_t)PPW * p.ops_lds_bytes);      // [lane][LANE_CACHE_BYTES / 8]
   bool active = lane < PPW && gid < p.n_work;
   uint32_t pair = 0;
   if (active) pair = p.work ? p.work[gid] : gid;
@@ -530,10 +553,8 @@ __global__ void __launch_bounds__(LANE_WAVES * 64) wfa_trace_lane_kernel(const W
   int plen = 0, tlen = 0, score = 0;
   const uint32_t* Pw = nullptr; const uint32_t* Tw = nullptr;
   if (active) {
-    const WfaSeqPair mp = p.meta[pair];
-    plen = (int)mp.pattern_len; tlen = (int)mp.text_len;
-    Pw = p.packed + ((RAW ? mp.pattern_offset : mp.pattern_offset_packed) >> 2);
-    Tw = p.packed + ((RAW ? mp.text_offset : mp.text_offset_packed) >> 2);
+    const PairSeqs sq = pair_seqs(p, pair, RAW);
+    plen = sq.plen; tlen = sq.tlen; Pw = sq.P; Tw = sq.T;
     score = p.score[pair];
   }
   stage_pairs(p, PPW, lane, active, plen, tlen, Pw, Tw, seq_lds);
@@ -541,7 +562,7 @@ __global__ void __launch_bounds__(LANE_WAVES * 64) wfa_trace_lane_kernel(const W
   bool fail = active && need_ops > (uint32_t)p.ops_lds_bytes;
   uint8_t* const q_end = ops_lds + (size_t)lane * p.ops_lds_bytes + need_ops;      // (the lane's slot: 4-byte aligned, like need_ops)
   uint32_t nops = 0;
-  if (active && !fail) fail = !walk_ops(p, pair, score, plen, tlen, q_end, need_ops, tab_cache + (size_t)lane * 9, nops);
+  if (active && !fail) fail = !walk_ops(p, pair, score, plen, tlen, q_end, need_ops, tab_cache + (size_t)lane * (LANE_CACHE_BYTES / 8), nops);
   const uint8_t* const q = q_end - nops;
   uint32_t len = 0;
   if (active && !fail) {
@@ -552,20 +573,9 @@ __global__ void __launch_bounds__(LANE_WAVES * 64) wfa_trace_lane_kernel(const W
   const unsigned long long txt_off = block_alloc<LANE_WAVES>(p.text_top, need_txt, wave_total, &block_base);
   if (active && !fail && txt_off + need_txt > p.text_cap) fail = true;
   if (active) {
-    if (!fail) {
-      int cost = 0;
-      replay<RAW>(q, nops, Pw, Tw, plen, tlen, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
-      p.cigar_off[pair] = txt_off;
-      p.cigar_len[pair] = len;
-      // (the text's own gap-affine cost must equal the score; adaptive band: the score follows the text -- see wfa_emit_kernel)
-      if (cost != score) {
-        if (p.score_fix) p.score_fix[pair] = cost;
-        else p.cigar_len[pair] = 0xFFFFFFFFu;
-      }
-    } else {
-      p.cigar_off[pair] = 0;
-      p.cigar_len[pair] = 0xFFFFFFFFu;
-    }
+    int cost = 0;
+    if (!fail) replay<RAW>(q, nops, Pw, Tw, plen, tlen, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
+    finish_pair(p, pair, fail, txt_off, len, cost, score);
   }
 }
 
@@ -593,12 +603,9 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_kernel(const WfaTraceP
   const uint8_t* q = nullptr; uint32_t nops = 0;
   bool fail = false;
   if (active) {
-    const WfaSeqPair mp = p.meta[pair];
-    plen = (int)mp.pattern_len; tlen = (int)mp.text_len;
-    Pw = p.packed + ((p.raw ? mp.pattern_offset : mp.pattern_offset_packed) >> 2);
-    Tw = p.packed + ((p.raw ? mp.text_offset : mp.text_offset_packed) >> 2);
-    const unsigned long long off = p.cigar_off[pair];
-    q = ((off & WFA_OPS_IN_ARENA) ? p.arena : p.ops) + (off & ~WFA_OPS_IN_ARENA);
+    const PairSeqs sq = pair_seqs(p, pair, p.raw);
+    plen = sq.plen; tlen = sq.tlen; Pw = sq.P; Tw = sq.T;
+    q = p.ops + p.cigar_off[pair];
     nops = p.cigar_len[pair];
     fail = nops == 0xFFFFFFFFu;
   }
@@ -608,12 +615,13 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_kernel(const WfaTraceP
     // long alignments (the wavefront kernel walked): the op lists -- thousands of operations, read four per load by ONE lane, a
     // round trip to L2 each time -- come into LDS too, after the sequences, copied by the whole wavefront
     uint32_t* const ops_l = seq_lds + (size_t)PPW * p.seq_lds_stride;
-    const uint32_t lwords = ((p.ops_slot >> 2) + 1u) | 1u;
+    const uint32_t lwords = emit_ops_words(p.ops_slot);
     const uint32_t my_words = (active && !fail) ? (nops + (uint32_t)(reinterpret_cast<uintptr_t>(q) & 3) + 3u) >> 2 : 0u;
     const uint32_t* const my_src = reinterpret_cast<const uint32_t*>(reinterpret_cast<uintptr_t>(q) & ~(uintptr_t)3);
     using GlobalWords = const __attribute__((address_space(1))) uint32_t*;
     for (int j = 0; j < PPW; ++j) {
       const uint32_t nw = __builtin_amdgcn_readlane(my_words, j);
+      // (readlane_ptr, spelled out: through the helper this instantiation takes two more vector registers)
       const uint32_t* src = reinterpret_cast<const uint32_t*>(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(reinterpret_cast<unsigned long long>(my_src) >> 32), j) << 32) |
                                                               (uint32_t)__builtin_amdgcn_readlane((int)reinterpret_cast<unsigned long long>(my_src), j));
       uint32_t* dst = ops_l + (size_t)j * lwords;
@@ -623,6 +631,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_kernel(const WfaTraceP
     // (a variable of its own: `q` stays a pointer to global memory for the compiler, this one a pointer to LDS)
     q_lds = reinterpret_cast<const uint8_t*>(ops_l + (size_t)lane * lwords) + (reinterpret_cast<uintptr_t>(q) & 3);
   }
+  SeqDirect pv{Pw}, tv{Tw};      // (the staged sequences, or the global ones)
   if (p.text_scratch) {
     // single replay: the text goes to this lane's slot of the scratch (sized by the same bound the host sizes the arenas
     // with: at most score / min(x, e) operations, each with a match run, item_chars characters per item); wfa_text_compact_kernel
@@ -632,29 +641,20 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_kernel(const WfaTraceP
     if (active && !fail && s_off + bound > p.text_scratch_cap) fail = true;
     if (active) {
       uint32_t len = 0xFFFFFFFFu;
+      int cost = 0;
       if (!fail) {
-        int cost = 0;
-        if constexpr (OPS_LDS)
-          len = p.raw ? replay<true, true>(q_lds, nops, Pw, Tw, plen, tlen, p.text_scratch + s_off, p.x, p.oe - p.e, p.e, &cost, bound, true)
-                      : replay<false, true>(q_lds, nops, Pw, Tw, plen, tlen, p.text_scratch + s_off, p.x, p.oe - p.e, p.e, &cost, bound, true);
-        else
-          len = p.raw ? replay<true>(q, nops, Pw, Tw, plen, tlen, p.text_scratch + s_off, p.x, p.oe - p.e, p.e, &cost, bound, true)
-                      : replay<false>(q, nops, Pw, Tw, plen, tlen, p.text_scratch + s_off, p.x, p.oe - p.e, p.e, &cost, bound, true);
+        len = replay_any<OPS_LDS>(p.raw, OPS_LDS ? q_lds : q, nops, pv, tv, plen, tlen, p.text_scratch + s_off, p.x, p.oe - p.e, p.e, &cost, bound, true);
         if (len != 0xFFFFFFFFu && len + 1u > bound) len = 0xFFFFFFFFu;
-        if (len != 0xFFFFFFFFu && cost != p.score[pair]) {
-          if (p.score_fix) p.score_fix[pair] = cost;
-          else len = 0xFFFFFFFFu;
-        }
       }
-      p.cigar_off[pair] = s_off;
-      p.cigar_len[pair] = len;
+      // (cigar_off: the text's place in the scratch until the compaction)
+      if (len != 0xFFFFFFFFu) finish_pair(p, pair, false, s_off, len, cost, p.score[pair]);
+      else finish_pair(p, pair, true);
     }
     return;
   }
   uint32_t len = 0;
   if (active && !fail) {
-    len = p.raw ? replay<true>(q, nops, Pw, Tw, plen, tlen, nullptr, 0, 0, 0, nullptr)
-                : replay<false>(q, nops, Pw, Tw, plen, tlen, nullptr, 0, 0, 0, nullptr);
+    len = replay_any(p.raw, q, nops, pv, tv, plen, tlen, (char*)nullptr, 0, 0, 0, (int*)nullptr);
     if (len == 0xFFFFFFFFu) fail = true;
   }
   const uint32_t need_txt = (active && !fail) ? len + 1u : 0u;
@@ -663,22 +663,9 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_kernel(const WfaTraceP
   if (active) {
     if (!fail) {
       int cost = 0;
-      if (p.raw) replay<true>(q, nops, Pw, Tw, plen, tlen, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
-      else replay<false>(q, nops, Pw, Tw, plen, tlen, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
-      p.cigar_off[pair] = txt_off;
-      p.cigar_len[pair] = len;
-      // The text's own gap-affine cost.  Exact alignments: it equals the wavefront score (checked: a
-      // difference would mean a broken trace).  Adaptive band: a path may open two gaps back to back
-      // where the extension cell had left the band; printed, they are one gap and cost less -- the
-      // reported score follows the alignment that is returned.
-      if (cost != p.score[pair]) {
-        if (p.score_fix) p.score_fix[pair] = cost;
-        else p.cigar_len[pair] = 0xFFFFFFFFu;
-      }
-    } else {
-      p.cigar_off[pair] = 0;
-      p.cigar_len[pair] = 0xFFFFFFFFu;
-    }
+      replay_any(p.raw, q, nops, pv, tv, plen, tlen, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
+      finish_pair(p, pair, false, txt_off, len, cost, p.score[pair]);
+    } else finish_pair(p, pair, true);
   }
 }
 
@@ -764,16 +751,14 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_wave_kernel(const Wfa
   for (uint32_t w = blockIdx.x; w < p.n_work; w += gridDim.x) {
     const uint32_t pair = __builtin_amdgcn_readfirstlane(p.work ? p.work[w] : w);
     if (p.status[pair] != WFA_ST_DONE) continue;
-    const WfaSeqPair mp = p.meta[pair];
-    const int plen = __builtin_amdgcn_readfirstlane((int)mp.pattern_len), tlen = __builtin_amdgcn_readfirstlane((int)mp.text_len);
+    // (pair_seqs and finish_pair, written out in this kernel: through the helpers its full path measured 1.8 % slower on 30 kbp reads)
+    PairSeqs sq = pair_seqs(p, pair, RAW);
+    const int plen = sq.plen = __builtin_amdgcn_readfirstlane(sq.plen), tlen = sq.tlen = __builtin_amdgcn_readfirstlane(sq.tlen);
     const int score = __builtin_amdgcn_readfirstlane(p.score[pair]);
-    const int sh = RAW ? 2 : 4;
-    const int pwords = ((plen + (1 << sh) - 1) >> sh) + 1, twords = ((tlen + (1 << sh) - 1) >> sh) + 1;
     if (!p.walk_only) {
-      const uint32_t* gp = p.packed + ((RAW ? mp.pattern_offset : mp.pattern_offset_packed) >> 2);
-      const uint32_t* gt = p.packed + ((RAW ? mp.text_offset : mp.text_offset_packed) >> 2);
-      for (int i = lane; i < pwords; i += 64) Pw[i] = gp[i];
-      for (int i = lane; i < twords; i += 64) Tw[i] = gt[i];
+      const int pwords = sq.pwords(), twords = sq.twords();
+      for (int i = lane; i < pwords; i += 64) Pw[i] = sq.P[i];
+      for (int i = lane; i < twords; i += 64) Tw[i] = sq.T[i];
     }
     // the reversed op list (every operation costs at least min(x, e) >= 1: `score` bytes suffice): in LDS when it
     // fits -- the replay reads one op per step, a round trip to L2 each if they sat in global memory --, else in the
@@ -808,28 +793,12 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_wave_kernel(const Wfa
         }
         if (q == q_begin) { fail = true; break; }
         const uint32_t code = tile[(s_top - s) * TILE_LDS_W + (k - kbase)];
-        uint8_t op;
-        if (state == 0) {
-          const uint32_t org = code & BT_M_MASK;
-          if (org == BT_M_X) { op = OP_X | OP_EXT_AFTER; s -= p.x; }
-          else if (org == BT_M_I) {
-            op = OP_I | OP_EXT_AFTER; --k;
-            if (code & BT_I_EXT) { s -= p.e; state = 1; } else { s -= p.oe; }
-          } else if (org == BT_M_D) {
-            op = OP_D | OP_EXT_AFTER; ++k;
-            if (code & BT_D_EXT) { s -= p.e; state = 2; } else { s -= p.oe; }
-          } else { fail = true; break; }
-        } else if (state == 1) {
-          op = OP_I; --k;
-          if (code & BT_I_EXT) { s -= p.e; } else { s -= p.oe; state = 0; }
-        } else {
-          op = OP_D; ++k;
-          if (code & BT_D_EXT) { s -= p.e; } else { s -= p.oe; state = 0; }
-        }
+        const uint32_t op = walk_step(code, state, s, k, p);
+        if (op == OP_NONE) { fail = true; break; }
         --q;
-        if (lane == 0) *q = op;
+        if (lane == 0) *q = (uint8_t)op;
       }
-      if (s != 0 || state != 0 || k != 0) fail = true;
+      if (!walk_ended(s, state, k)) fail = true;
     }
     // the op list is read back by this same wavefront: make lane 0's stores visible to all lanes
     __threadfence_block();
@@ -839,6 +808,8 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_wave_kernel(const Wfa
       // the list goes to (or is already in) this work item's slot of the global scratch, where wfa_emit_kernel looks for it
       uint8_t* const g_end = p.ops + (size_t)w * p.ops_slot + need_ops;
       if (!fail && q_begin == ops_lds) { for (uint32_t i = lane; i < nops; i += 64) g_end[(long)i - (long)nops] = q[i]; }
+      // (not finish_pair's tail: this is the walk's result -- where the op list is and how long -- as wfa_walk_kernel leaves it;
+      // there is no text yet and no cost to compare)
       if (lane == 0) {
         p.cigar_off[pair] = fail ? 0ull : (unsigned long long)(g_end - nops - p.ops);
         p.cigar_len[pair] = fail ? 0xFFFFFFFFu : nops;
@@ -897,7 +868,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_group_kernel(const Wf
   extern __shared__ __attribute__((aligned(16))) uint32_t glds[];
   constexpr int L = 64 / G, TILE_H = L;       // one row per lane of the group (short alignments: taller tiles cost more than they save)
   const int lane = threadIdx.x & 63, grp = lane / L, sub = lane % L, lead = grp * L;
-  const size_t share_words = ((size_t)2 * p.seq_words_cap * 4 + (size_t)TILE_H * TILE_LDS_W + (size_t)p.ops_lds_bytes + (size_t)p.text_lds_bytes + 15) / 16 * 4;
+  const size_t share_words = group_share_bytes(G, p.seq_words_cap, p.ops_lds_bytes, p.text_lds_bytes) / 4;
   uint32_t* Pw = glds + (size_t)grp * share_words;
   uint32_t* Tw = Pw + p.seq_words_cap;
   uint8_t* tile = reinterpret_cast<uint8_t*>(Tw + p.seq_words_cap);       // [L rows][32 bytes]
@@ -909,16 +880,13 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_group_kernel(const Wf
     uint32_t pair = 0;
     if (active) pair = p.work ? p.work[w] : w;
     if (active && p.status[pair] != WFA_ST_DONE) active = false;
-    int plen = 0, tlen = 0, score = 0, pwords = 0, twords = 0;
+    int plen = 0, tlen = 0, score = 0;
     if (active) {
-      const WfaSeqPair mp = p.meta[pair];
-      plen = (int)mp.pattern_len; tlen = (int)mp.text_len; score = p.score[pair];
-      const int sh = RAW ? 2 : 4;
-      pwords = ((plen + (1 << sh) - 1) >> sh) + 1; twords = ((tlen + (1 << sh) - 1) >> sh) + 1;
-      const uint32_t* gp = p.packed + ((RAW ? mp.pattern_offset : mp.pattern_offset_packed) >> 2);
-      const uint32_t* gt = p.packed + ((RAW ? mp.text_offset : mp.text_offset_packed) >> 2);
-      for (int i = sub; i < pwords; i += L) Pw[i] = gp[i];
-      for (int i = sub; i < twords; i += L) Tw[i] = gt[i];
+      const PairSeqs sq = pair_seqs(p, pair, RAW);
+      plen = sq.plen; tlen = sq.tlen; score = p.score[pair];
+      const int pwords = sq.pwords(), twords = sq.twords();
+      for (int i = sub; i < pwords; i += L) Pw[i] = sq.P[i];
+      for (int i = sub; i < twords; i += L) Tw[i] = sq.T[i];
     }
     const uint32_t need_ops = active ? (((uint32_t)score + 3u) & ~3u) : 0u;
     bool fail = false;
@@ -946,28 +914,12 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_group_kernel(const Wf
         }
         if (q == q_begin) { fail = true; break; }
         const uint32_t code = tile[(s_top - s) * TILE_LDS_W + (k - kbase)];
-        uint8_t op;
-        if (state == 0) {
-          const uint32_t org = code & BT_M_MASK;
-          if (org == BT_M_X) { op = OP_X | OP_EXT_AFTER; s -= p.x; }
-          else if (org == BT_M_I) {
-            op = OP_I | OP_EXT_AFTER; --k;
-            if (code & BT_I_EXT) { s -= p.e; state = 1; } else { s -= p.oe; }
-          } else if (org == BT_M_D) {
-            op = OP_D | OP_EXT_AFTER; ++k;
-            if (code & BT_D_EXT) { s -= p.e; state = 2; } else { s -= p.oe; }
-          } else { fail = true; break; }
-        } else if (state == 1) {
-          op = OP_I; --k;
-          if (code & BT_I_EXT) { s -= p.e; } else { s -= p.oe; state = 0; }
-        } else {
-          op = OP_D; ++k;
-          if (code & BT_D_EXT) { s -= p.e; } else { s -= p.oe; state = 0; }
-        }
+        const uint32_t op = walk_step(code, state, s, k, p);
+        if (op == OP_NONE) { fail = true; break; }
         --q;
-        if (sub == 0) *q = op;
+        if (sub == 0) *q = (uint8_t)op;
       }
-      if (s != 0 || state != 0 || k != 0) fail = true;
+      if (!walk_ended(s, state, k)) fail = true;
     }
     __threadfence_block();
     __builtin_amdgcn_wave_barrier();
@@ -993,19 +945,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_group_kernel(const Wf
         replay<RAW>(q, nops, Pw, Tw, plen, tlen, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
       }
     }
-    if (active && sub == 0) {
-      if (!fail) {
-        p.cigar_off[pair] = txt_off;
-        p.cigar_len[pair] = len;
-        if (cost != score) {
-          if (p.score_fix) p.score_fix[pair] = cost;
-          else p.cigar_len[pair] = 0xFFFFFFFFu;
-        }
-      } else {
-        p.cigar_off[pair] = 0;
-        p.cigar_len[pair] = 0xFFFFFFFFu;
-      }
-    }
+    if (active && sub == 0) finish_pair(p, pair, fail, txt_off, len, cost, score);
     __builtin_amdgcn_wave_barrier();      // (the next alignments overwrite the staged sequences)
   }
 }
@@ -1023,8 +963,7 @@ void allow_lds(K kernel, size_t lds, size_t (&allowed)[16]) {
 
 template <bool RAW, int G>
 void launch_group(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
-  const size_t share = ((size_t)2 * p.seq_words_cap * 4 + (size_t)(64 / G) * TILE_LDS_W + (size_t)p.ops_lds_bytes + (size_t)p.text_lds_bytes + 15) / 16 * 16;
-  const size_t lds = share * G;
+  const size_t lds = group_kernel_lds_bytes(G, p.seq_words_cap, p.ops_lds_bytes, p.text_lds_bytes);
   const uint32_t blocks = (p.n_work + G - 1) / G;
   const uint32_t grid = blocks < 8192u ? blocks : 8192u;
   static thread_local size_t allowed[16] = {0};
@@ -1034,8 +973,7 @@ void launch_group(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0, h
 
 template <bool RAW>
 void launch_wave(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
-  const size_t lds = p.walk_only ? (size_t)64 * TILE_LDS_W + (size_t)p.ops_lds_bytes
-                                 : (size_t)2 * p.seq_words_cap * 4 + 64 * TILE_LDS_W + (size_t)p.ops_lds_bytes + (size_t)p.text_lds_bytes;
+  const size_t lds = p.walk_only ? wave_walk_lds_bytes(p.ops_lds_bytes) : wave_kernel_lds_bytes(p.seq_words_cap, p.ops_lds_bytes, p.text_lds_bytes);
   const uint32_t grid = p.n_work < 8192u ? p.n_work : 8192u;
   static thread_local size_t allowed[16] = {0};
   allow_lds(wfa_trace_wave_kernel<RAW>, lds, allowed);
@@ -1060,23 +998,25 @@ bool wfa_launch_trace(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev
     if (p.raw) launch_wave<true>(p, stream, ev0, ev1); else launch_wave<false>(p, stream, ev0, ev1);
     return true;
   }
+  // the staged replay, then -- where its texts went to a scratch -- their compaction
+  auto emit_then_compact = [&](auto kernel, const size_t lds, size_t (&allowed)[16]) {
+    allow_lds(kernel, lds, allowed);
+    const dim3 grid_e((p.n_work + (uint32_t)p.emit_pairs - 1) / (uint32_t)p.emit_pairs);
+    wfa_launch_timed(kernel, grid_e, dim3(TRACE_THREADS), lds, stream, (hipEvent_t) nullptr, p.text_scratch ? (hipEvent_t) nullptr : ev1, p);
+    if (p.text_scratch)
+      wfa_launch_timed(wfa_text_compact_kernel, dim3((p.n_work + COMPACT_WAVES * 64 - 1) / (COMPACT_WAVES * 64)), dim3(COMPACT_WAVES * 64), 0, stream, (hipEvent_t) nullptr, ev1, p);
+  };
   if (p.wave_kernel) {
     // long alignments: the wavefront kernel walks, the lane kernel replays (a few pairs per wavefront staged in LDS)
     if (p.raw) launch_wave<true>(p, stream, ev0, (hipEvent_t) nullptr); else launch_wave<false>(p, stream, ev0, (hipEvent_t) nullptr);
-    const size_t lds_e = (size_t)p.emit_pairs * ((size_t)p.seq_lds_stride * 4 + (size_t)((((p.ops_slot >> 2) + 1u) | 1u) * 4u));
     static thread_local size_t allowed_e[16] = {0};
-    allow_lds(wfa_emit_kernel<true, true>, lds_e, allowed_e);
-    const dim3 grid_e((p.n_work + (uint32_t)p.emit_pairs - 1) / (uint32_t)p.emit_pairs);
-    wfa_launch_timed(wfa_emit_kernel<true, true>, grid_e, dim3(TRACE_THREADS), lds_e, stream, (hipEvent_t) nullptr, p.text_scratch ? (hipEvent_t) nullptr : ev1, p);
-    if (p.text_scratch)
-      wfa_launch_timed(wfa_text_compact_kernel, dim3((p.n_work + COMPACT_WAVES * 64 - 1) / (COMPACT_WAVES * 64)), dim3(COMPACT_WAVES * 64), 0, stream, (hipEvent_t) nullptr, ev1, p);
+    emit_then_compact(wfa_emit_kernel<true, true>, emit_ops_kernel_lds_bytes(p.emit_pairs, p.seq_lds_stride, p.ops_slot), allowed_e);
     return true;
   }
   const dim3 grid((p.n_work + TRACE_THREADS - 1) / TRACE_THREADS), block(TRACE_THREADS);
   if (p.lane_fused) {
-    // short alignments: walk + both replays in one kernel, op lists in LDS (sequences, then ops_lds_bytes per lane, then 72 bytes of
-    // row-table cache per lane)
-    const size_t lds = (size_t)LANE_WAVES * lane_kernel_wave_bytes(p.emit_pairs, p.seq_lds_stride, p.ops_lds_bytes);
+    // short alignments: walk + both replays in one kernel, op lists in LDS
+    const size_t lds = lane_kernel_lds_bytes(p.emit_pairs, p.seq_lds_stride, p.ops_lds_bytes);
     const uint32_t per_block = (uint32_t)LANE_WAVES * (uint32_t)p.emit_pairs;
     const dim3 grid_f((p.n_work + per_block - 1) / per_block), block_f(LANE_WAVES * 64);
     static thread_local size_t allowed[2][16] = {{0}};
@@ -1086,19 +1026,13 @@ bool wfa_launch_trace(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev
   }
   uint32_t walk_grid = (p.n_work + WALK_WAVES * 64 - 1) / (WALK_WAVES * 64);
   if (p.walk_grid_cap > 0 && walk_grid > (uint32_t)p.walk_grid_cap) walk_grid = (uint32_t)p.walk_grid_cap;
-  hipEvent_t ev_first = ev0;      // (start of whichever kernel comes first)
-  if (!p.skip_walk) { wfa_launch_timed(wfa_walk_kernel, dim3(walk_grid), dim3(WALK_WAVES * 64), 0, stream, ev0, (hipEvent_t) nullptr, p); ev_first = nullptr; }
+  wfa_launch_timed(wfa_walk_kernel, dim3(walk_grid), dim3(WALK_WAVES * 64), 0, stream, ev0, (hipEvent_t) nullptr, p);
   if (p.seq_lds_stride == 0) {      // (sequences too long to stage 64 pairs, or tuning.trace_mode 1: 8-word LDS windows)
-    wfa_launch_timed(wfa_emit_win_kernel, grid, block, 0, stream, ev_first, ev1, p);
+    wfa_launch_timed(wfa_emit_win_kernel, grid, block, 0, stream, (hipEvent_t) nullptr, ev1, p);
     return true;
   }
-  const size_t lds = (size_t)p.emit_pairs * p.seq_lds_stride * 4;
   static thread_local size_t allowed[16] = {0};
-  allow_lds(wfa_emit_kernel<true, false>, lds, allowed);
-  const dim3 grid_e((p.n_work + (uint32_t)p.emit_pairs - 1) / (uint32_t)p.emit_pairs);
-  wfa_launch_timed(wfa_emit_kernel<true, false>, grid_e, block, lds, stream, ev_first, p.text_scratch ? (hipEvent_t) nullptr : ev1, p);
-  if (p.text_scratch)
-    wfa_launch_timed(wfa_text_compact_kernel, dim3((p.n_work + COMPACT_WAVES * 64 - 1) / (COMPACT_WAVES * 64)), dim3(COMPACT_WAVES * 64), 0, stream, (hipEvent_t) nullptr, ev1, p);
+  emit_then_compact(wfa_emit_kernel<true, false>, emit_kernel_lds_bytes(p.emit_pairs, p.seq_lds_stride), allowed);
   return true;
 }
 

@@ -56,11 +56,14 @@ enum : uint32_t { BT_M_NONE = 0, BT_M_X = 12, BT_M_D = 8, BT_M_I = 4, BT_M_MASK 
 // Operations of a reversed op list (what the backward walk leaves for the replay): the kind, and whether a run of matches
 // follows the operation (re-derived by the replay as a longest common prefix).
 enum : uint8_t { OP_X = 1, OP_I = 2, OP_D = 3, OP_EXT_AFTER = 0x10 };
-// cigar_off of an alignment between walk and replay: byte offset of its op list -- in the op scratch, or (this bit set) in the
-// backtrace ARENA, where the one-wave wavefront kernels leave it when they walk their own alignments (WfaAlignParams::walk_in_kernel)
-#define WFA_OPS_IN_ARENA (1ull << 63)
 
+// First word of a pair's block in the arena: this value marks the TILES layout; anything else is entry 0 of a ROWS row table.  The
+// marker is in band, its one reader (bt_block, trace_kernel.hip) relies on two facts:
+//   * every ROWS producer writes word 0 of its table (the arena unit of the row of score 0);
+//   * an arena unit can never equal the marker: the arena is capped at WFA_ARENA_MAX_BYTES, its 16-byte units stay below 2^32 - 256.
 #define WFA_ROW_NONE 0xFFFFFFFFu
+constexpr unsigned long long WFA_ARENA_MAX_BYTES = (1ull << 36) - 4096;
+static_assert(WFA_ARENA_MAX_BYTES / 16 < WFA_ROW_NONE, "a row unit must never read as the TILES marker");
 // The lean cells of the 16-bit LDS tiers (0, 1, 2, 4) never switch a lane off: the lanes of a row's last 64-diagonal
 // chunk that lie beyond its upper limit store NULL offsets into that many cells behind the row (every ring row carries
 // WFA_RING_ROW_PAD extra cells for it) and origin bytes behind the row's bytes in the arena (every arena chunk keeps
@@ -116,10 +119,6 @@ struct WfaAlignParams {
   unsigned long long* arena_top;         // bump pointer (units)
   uint32_t chunk_units;          // refill granularity
   uint32_t* bt_final_row;        // [pair] out: unit offset of the pair's block of tiles / row table
-  // (round 5's option -- the one-wave tiers walking a finished alignment back themselves, a measured loss -- is gone: always 0)
-  int walk_in_kernel;
-  unsigned long long* cigar_off; // [pair] out (walk_in_kernel): WFA_OPS_IN_ARENA | byte offset of the op list in the arena
-  uint32_t* cigar_len;           // [pair] out (walk_in_kernel): number of operations
   // global-memory ring (only the GLOBAL_RING instantiation)
   void* gring;                   // per-block slices of gring_stride bytes
   int ring16;                    //   16-bit offsets in it (sequences <= 32766 bases), else 32-bit
@@ -147,7 +146,6 @@ struct WfaTraceParams {
   int group;                     // wave kernel: alignments per wavefront (1, 2, 4 or 8: 64/group lanes each, own LDS share)
   int lane_fused;                // lane-per-alignment path: walk + replay in ONE kernel, op lists of ops_lds_bytes per lane in LDS (short alignments)
   int walk_grid_cap;             // workgroups of wfa_walk_kernel (it strides over the list); 0: one per 256 list entries
-  int skip_walk;                 // lane path: every finished pair of the list was walked by its wavefront kernel: no wfa_walk_kernel
   int walk_only;                 // wave kernel: only the walk (op list -> slot w of ops_slot bytes in the global scratch); wfa_emit_kernel replays
   uint32_t ops_slot;
   int seq_words_cap;             // wave kernel: LDS words reserved per sequence
@@ -169,7 +167,7 @@ struct WfaTraceParams {
   unsigned long long* scratch_top;
   int min_op_cost;               // min(x, e): an alignment of score s has at most s / min_op_cost operations
   int item_chars;                // widest RLE item (digits of the longest sequence + 1): sizes the upper-bound text slots
-  unsigned long long* cigar_off; // [pair] out: byte offset of the CIGAR in `text`
+  unsigned long long* cigar_off; // [pair] out: byte offset of the CIGAR in `text` (between walk and replay: of the op list in `ops`)
   uint32_t* cigar_len;           // [pair] out: strlen; 0xFFFFFFFF if it did not fit
 };
 

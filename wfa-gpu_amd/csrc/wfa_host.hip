@@ -24,6 +24,7 @@
 
 #include "../../include/wfa_gpu_device.h"
 #include "wfa_device.h"
+#include "trace_layout.h"
 
 static_assert(sizeof(sequence_pair_t) == sizeof(WfaSeqPair), "ABI mirror");
 
@@ -795,7 +796,7 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
         want = std::min(want, std::max<size_t>(lim, (size_t)64 << 20));
       }
     }
-    want = std::min<size_t>(want, ((size_t)1 << 36) - 4096);
+    want = std::min<size_t>(want, (size_t)WFA_ARENA_MAX_BYTES);
     if (c->arena.cap < want && c->arena.ensure(want, st)) return -1;
     ap.arena = static_cast<uint8_t*>(c->arena.p);
     ap.arena_units = c->arena.cap / 16 - 8;      // (128 bytes of slack: the walk reads row-table entries a line at a time)
@@ -904,7 +905,7 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
       unfinished_at_sync = -1;      // (work is being queued: the last count is history)
       uint32_t* const chain_list = cur;
       const uint32_t n_chain = n_cur;
-      struct Link { int tier; int ct_list; int ct_cells; hipEvent_t e0, e1; bool banded; bool budgeted; bool first_round; uint32_t n_in; bool walked; } link[2];
+      struct Link { int tier; int ct_list; int ct_cells; hipEvent_t e0, e1; bool banded; bool budgeted; bool first_round; uint32_t n_in; } link[2];
       int n_links = 0;
       bool fused_tail = false; uint32_t* tail_out = nullptr; unsigned long long* tail_count = nullptr; unsigned long long* tail_parts_out = nullptr;
       bool solo = false, parts_on_host = false, skip_read = false; uint32_t parts_n = 0;      // (see the launch below)
@@ -916,7 +917,7 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
       for (;;) {
         Link& L = link[n_links];
         L = {0, n_links ? CT_LIST2 : CT_LIST, n_links ? CT_LCELLS2 : CT_LCELLS, n_links ? c->ev_b0 : c->ev_a0, n_links ? c->ev_b1 : c->ev_a1,
-             false, budget_round, round == 0, n_cur, false};
+             false, budget_round, round == 0, n_cur};
         if (!have_start) { L.e0 = c->ev_start; have_start = true; }      // (the call's first kernel: its start stamp is the call's)
         TierPlan tp;
         ap.budget = budget_round ? budgets : nullptr;
@@ -966,12 +967,6 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
           if (c->gring.ensure(stride * g, st)) return -1;
           ap.gring = c->gring.p; ap.gring_stride = stride;
         }
-        // (tuning.kernel_walk -- the one-wave kernels walking their own alignments back, measured a loss in round 5 -- went with the row
-        // table it read: round 6's tiles make wfa_walk_kernel itself cheap)
-        L.walked = false;
-        ap.walk_in_kernel = 0;
-        ap.cigar_off = static_cast<unsigned long long*>(c->cig_off[c->out_set].p);
-        ap.cigar_len = static_cast<uint32_t*>(c->cig_len[c->out_set].p);
         ap.dbg_times = nullptr; ap.dbg_cap = 0;
         if (c->tuning.timed_barriers && round == 0 && cigar_now && !raw && !L.banded && (tp.tier == 1 || tp.tier == 4)) {
           const int nw = tp.tier == 1 ? 4 : 16;
@@ -1126,39 +1121,11 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
                                static_cast<const uint32_t*>(c->status.p), (const int32_t*)d_scores,
                                static_cast<const uint32_t*>(c->cells.p), std::min(pen.x, pen.e), item_chars, ct, n);
       if (cigar_now) {
-        WfaTraceParams tp{};
-        tp.raw = raw ? 1 : 0;
-        // both sequences of a pair, as words, per lane; staged in LDS when 64 lanes fit 48 KiB
-        const unsigned per_seq = raw ? (max_len + 3) / 4 + 1 : (max_len + 15) / 16 + 1;
-        const unsigned stride = (2 * per_seq) | 1u;
-        tp.seq_lds_stride = ((size_t)64 * stride * 4 <= (48u << 10) && c->tuning.trace_mode != 1) ? (int)stride : 0;
-        // alignments per wavefront of the staged replay: as many as still leave a CU eight wavefronts (two per SIMD).  LDS decides:
-        // 1 kbp reads at 64 per wavefront are 4 wavefronts per CU, one per SIMD, every dependent LDS read of the replay exposed;
-        // measured on BASELINE configs[2] (trace ms per 1M pairs): 64: 4.14, 56: 3.92, 48: 3.84, 40: 3.84, 32: 3.79, 24: 3.82
-        tp.emit_pairs = 64;
-        if (tp.seq_lds_stride > 0) {
-          while (tp.emit_pairs > 16 && c->lds_per_block_max / ((size_t)tp.emit_pairs * stride * 4) < 8) tp.emit_pairs -= 8;
-          const int forced = c->tuning.emit_pairs;
-          if (forced >= 8 && forced <= 64) tp.emit_pairs = forced & ~7;
-        }
-        // sequences too long to stage 64 pairs per wavefront: one wavefront per alignment (sequences of ONE pair in LDS)
-        tp.seq_words_cap = (int)per_seq + 1;
-        // (it needs both sequences of a pair plus ~1 KiB in LDS; sequences at the very edge of what the align tiers stage do
-        // not leave that: the lane-per-alignment walk + windowed emit take any length)
-        tp.wave_kernel = (tp.seq_lds_stride == 0 && c->tuning.trace_mode != 1 &&
-                          (size_t)2 * tp.seq_words_cap * 4 + 64 * 32 + 64 <= c->lds_per_block_max) ? 1 : 0;      // (64 * 32: the tile, trace_kernel.hip TILE_LDS_W)
-        // Scratch sizes.  Lane-per-alignment kernels with a bounded score: from the bound (no pair of the chain finished
-        // above s_hi), no round trip.  The wave kernels size their LDS from the largest score of the pass and the
-        // unbounded tier has no bound: those read the sums k_trace_bounds has just formed.
-        const unsigned long long ops_bound = (unsigned long long)n_chain * (((unsigned long long)std::max<long long>(s_hi, 0) + 3ull) & ~3ull);
-        const unsigned long long text_bound = (unsigned long long)n_chain *
-            ((unsigned long long)item_chars * (2ull * (unsigned long long)(std::max<long long>(s_hi, 0) / std::min(pen.x, pen.e)) + 1ull) + 1ull);
-        // (the bound is sized by the chain's largest budget -- the caller's max_error once a re-run link follows -- for EVERY pair:
-        // fine for the batches of a pipelined call, whose round trips it saves (62 500 x 1 kbp pairs: 225 MB), too generous for a
-        // big resident batch (1M pairs at max_error 300: 3.6 GB of fresh device memory per buffer to save one counter read)
-        const bool by_bound = !tp.wave_kernel && s_hi >= 0 && s_hi <= 30000 && text_bound <= ((unsigned long long)768 << 20);
+        // which kernels walk and replay (trace_layout.h: two steps, the largest score of the pass arrives with the counters)
+        const TracePlanIn plan_in{c->lds_per_block_max, c->tuning.trace_mode, c->tuning.emit_pairs, raw, max_len, n_chain, s_hi, std::min(pen.x, pen.e), item_chars};
+        TracePlan plan = trace_plan_begin(plan_in);
         unsigned long long ops_need, text_sum;
-        if (by_bound) { ops_need = ops_bound + 256; text_sum = text_bound; }
+        if (plan.by_bound) { ops_need = plan.ops_bound + 256; text_sum = plan.text_bound; }
         else {
           // (a chain without a tail kernel: nobody has formed the sums yet.  Cells and the unfinished count stay with the launch's
           // partial sums)
@@ -1167,66 +1134,22 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
           if (read_counters(c)) return -1;
           ops_need = c->h_counters[CT_SUM_OPS] + 256; text_sum = c->h_counters[CT_SUM_TEXT];
         }
+        trace_plan_finish(plan, plan_in, c->h_counters[CT_MAX_SCORE]);
         const unsigned long long text_need = text_used + text_sum + 256;
         if (c->ops.ensure(ops_need, st)) return -1;
         if (c->text[c->out_set].ensure(std::max<size_t>(text_need, c->text_cfg), st, text_used)) return -1;
         if (!c->text[c->out_set ^ 1].p && c->text[c->out_set ^ 1].ensure(c->text[c->out_set].cap, st)) return -1;      // (the next call's set: see above)
-        {
-          // op list (one byte per score point of the largest score of the pass) and CIGAR text of one alignment in LDS,
-          // within 40 KiB per wavefront so that at least four of them fit a CU
-          const size_t seq_b = (size_t)2 * tp.seq_words_cap * 4 + 2048;      // (+ the tile: 64 rows of 32 bytes)
-          size_t room = seq_b < (40u << 10) ? (40u << 10) - seq_b : 0;
-          const size_t smax = by_bound ? (size_t)s_hi : (size_t)c->h_counters[CT_MAX_SCORE];
-          tp.ops_lds_bytes = (int)(((smax + 3) & ~(size_t)3) <= room ? ((smax + 15) & ~(size_t)15) : 0);
-          room -= (size_t)tp.ops_lds_bytes;
-          tp.text_lds_bytes = (int)(std::min<size_t>(room, 2 * smax + 64) & ~(size_t)15);
-          // Several alignments per wavefront (64/G lanes and one LDS share each) for SHORT op lists only (2 kbp reads, G = 8:
-          // 262k pairs 13.2 -> 6.6 ms).  With hundreds of operations per alignment the replays of the groups diverge and
-          // the wavefront per alignment wins again (16k x 10 kbp: 2.7 ms against 4.0 ms with G = 4).
-          const size_t share = seq_b - 2048 + (size_t)tp.ops_lds_bytes + (size_t)tp.text_lds_bytes;
-          tp.group = 1;
-          if (c->tuning.trace_mode == 0 && tp.ops_lds_bytes > 0 && smax <= 512)
-            for (int g = 8; g >= 2; g >>= 1)
-              if ((share + (size_t)(64 / g) * 32 + 16) * g <= (40u << 10) && n_chain >= (uint32_t)g * 1024u) { tp.group = g; break; }
+        if (plan.walk_only) {
+          // (op lists in slots of the largest score of the pass)
+          if (c->ops.ensure((unsigned long long)n_chain * plan.ops_slot + 256, st)) return -1;
+          c->stats.pairs_trace_split += n_chain;
         }
-        // LONG alignments, one wavefront each: the wavefront kernel only walks; the replay is the staged lane-per-alignment kernel's
-        // with as many pairs per wavefront (8, 16, ...) as fit LDS next to three more wavefronts (a replay is one serial chain:
-        // run by a whole wavefront it is 64 lanes executing the same chain).  Op lists in slots of the largest score of the pass.
-        tp.walk_only = 0;
-        const unsigned long long slot = ((unsigned long long)c->h_counters[CT_MAX_SCORE] + 3ull) & ~3ull;
-        const size_t per_pair = (size_t)stride * 4 + (size_t)slot + 8;      // LDS of one alignment of the replay: sequences + op list
-        // (big passes only: a replay step takes a lane of the lane kernel -- its neighbours in other branches -- 1.3 us against the 0.4 us
-        // of a wavefront with a SIMD to itself; with thousands of alignments the wavefronts share SIMDs five at a time and the lanes
-        // win: 16 384 x 10 kbp at 3 %, trace 2.22 -> 2.04 ms.  tuning.trace_mode 4: whatever the size of the pass -- tests)
-        if (tp.wave_kernel && tp.group == 1 && c->tuning.trace_mode != 2 && (n_chain >= 8192u || c->tuning.trace_mode == 4) &&
-            8 * per_pair <= c->lds_per_block_max) {
-          if ((unsigned long long)n_chain * slot <= (1ull << 30)) {
-            if (c->ops.ensure((unsigned long long)n_chain * slot + 256, st)) return -1;
-            tp.walk_only = 1; tp.ops_slot = (uint32_t)slot;
-            c->stats.pairs_trace_split += n_chain;
-            tp.seq_lds_stride = (int)stride;
-            tp.emit_pairs = 8;
-            while (tp.emit_pairs < 64 && (size_t)(tp.emit_pairs + 8) * per_pair * 4 <= c->lds_per_block_max) tp.emit_pairs += 8;
-            const int forced = c->tuning.emit_pairs;
-            if (forced >= 8 && forced <= 64 && (size_t)(forced & ~7) * per_pair <= c->lds_per_block_max) tp.emit_pairs = forced & ~7;
-            // (the walk keeps its op list in LDS when it fits: ops_lds_bytes from above, without the sequences)
-            const size_t smax = (size_t)c->h_counters[CT_MAX_SCORE];
-            tp.ops_lds_bytes = (int)(smax + 16 <= (39u << 10) ? ((smax + 15) & ~(size_t)15) : 0);
-            tp.text_lds_bytes = 0;
-          }
-        }
-        // SHORT alignments (no pair of the chain finished above a score of 124): walk and replay in one kernel, op lists in LDS
-        tp.lane_fused = 0;
-        if (!tp.wave_kernel && tp.seq_lds_stride > 0 && s_hi >= 0 && s_hi <= 124 && c->tuning.trace_mode != 3) {
-          tp.lane_fused = 1;
-          tp.ops_lds_bytes = (int)((s_hi + 3) & ~3ll);
-          if (!(c->tuning.emit_pairs >= 8 && c->tuning.emit_pairs <= 64)) {
-            tp.emit_pairs = 64;
-            while (tp.emit_pairs > 16 && c->lds_per_block_max / ((size_t)tp.emit_pairs * (stride * 4 + (size_t)tp.ops_lds_bytes) + 64 * 72) < 8) tp.emit_pairs -= 8;
-          }
-          // (the kernel's workgroups are four wavefronts with a share of LDS each: trace_kernel.hip, LANE_WAVES)
-          while (tp.emit_pairs > 8 && 4 * ((size_t)tp.emit_pairs * (stride * 4 + (size_t)tp.ops_lds_bytes) + 64 * 72 + 16) > c->lds_per_block_max) tp.emit_pairs -= 8;
-        }
+        WfaTraceParams tp{};
+        tp.raw = raw ? 1 : 0;
+        tp.seq_lds_stride = plan.seq_lds_stride; tp.emit_pairs = plan.emit_pairs; tp.seq_words_cap = plan.seq_words_cap;
+        tp.wave_kernel = plan.wave_kernel; tp.group = plan.group; tp.lane_fused = plan.lane_fused;
+        tp.walk_only = plan.walk_only; tp.ops_slot = plan.ops_slot;
+        tp.ops_lds_bytes = plan.ops_lds_bytes; tp.text_lds_bytes = plan.text_lds_bytes;
         tp.packed = ap.packed; tp.meta = ap.meta; tp.work = chain_list; tp.n_work = n_chain;
         tp.x = pen.x; tp.oe = oe; tp.e = pen.e;
         tp.score = d_scores; tp.status = static_cast<const uint32_t*>(c->status.p);
@@ -1236,11 +1159,7 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
         tp.text = static_cast<char*>(c->text[c->out_set].p); tp.text_cap = c->text[c->out_set].cap; tp.text_top = ct + CT_TEXT;
         tp.min_op_cost = std::min(pen.x, pen.e);
         tp.item_chars = item_chars;
-        // lane-per-alignment emit with whole sequences staged: one replay into a scratch + compaction (big passes only: the
-        // scratch holds the upper bounds, ~3x the text)
-        // (long alignments replayed by the lane kernel -- walk_only -- always: a second replay of hundreds of operations costs more than
-        // the compaction launch)
-        if (((!tp.wave_kernel && n_chain >= 8192u) || tp.walk_only) && !tp.lane_fused && tp.seq_lds_stride > 0) {
+        if (plan.text_scratch) {
           if (c->text_scratch.ensure(text_sum + 4096, st)) return -1;
           if (zero_counter(c, CT_SCRATCH)) return -1;
           tp.text_scratch = static_cast<char*>(c->text_scratch.p); tp.text_scratch_cap = c->text_scratch.cap; tp.scratch_top = ct + CT_SCRATCH;
@@ -1249,10 +1168,6 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
         tp.cigar_len = static_cast<uint32_t*>(c->cig_len[c->out_set].p);
         // (ev_t0 / ev_t1: start of the first and end of the last backtrace kernel)
         tp.walk_grid_cap = 2 * c->num_cus;      // (two workgroups = eight wavefronts per CU: trace_kernel.hip, wfa_walk_kernel)
-        // (every link of the chain walked its own alignments: no wfa_walk_kernel; a mixed chain runs it, and it skips the walked pairs)
-        tp.skip_walk = 1;
-        for (int l = 0; l < n_links; ++l) if (!link[l].walked) tp.skip_walk = 0;
-        if (tp.skip_walk) c->stats.pairs_walked_in_kernel += n_chain;
         traced = wfa_launch_trace(tp, st, c->ev_t0, c->ev_t1);
         HIP_TRY(hipGetLastError());
         // ---- pairs that ran out of arena go into the next pass (CIGAR calls only: score-only calls have no arena) ----
@@ -1327,7 +1242,7 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
       // progress at all, also halve the number of alignments in flight
       size_t free_b = 0, total_b = 0;
       HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-      const size_t limit = std::min<size_t>((size_t)(0.6 * (double)(free_b + c->arena.cap)), ((size_t)1 << 36) - 4096);
+      const size_t limit = std::min<size_t>((size_t)(0.6 * (double)(free_b + c->arena.cap)), (size_t)WFA_ARENA_MAX_BYTES);
       const size_t grown = std::min<size_t>(limit, std::max<size_t>(2 * c->arena.cap, c->arena.cap + ((size_t)256 << 20)));
       const bool can_grow = !c->arena_cfg && grown > c->arena.cap;
       if (can_grow) {
