@@ -210,6 +210,29 @@ int wfagpu_amd_align_device(wfagpu_amd_ctx_t* ctx, const wfagpu_amd_batch_t* bat
                             const char** d_text, const unsigned long long** d_off,
                             const unsigned int** d_len);
 
+/* Ends-free (semi-global) alignment, WFA2's wavefront_aligner_set_alignment_free_ends: up to pattern_begin_free bases at the
+ * start of the pattern (text_begin_free of the text) may stay in front of the alignment, up to pattern_end_free
+ * (text_end_free) behind it, at no cost.  Each value is clamped to the length of its sequence, pair by pair (INT_MAX:
+ * entirely free).  Scores and CIGARs are WFA2's; the CIGAR covers both whole sequences, the free bases as D (pattern) or I
+ * (text) runs at its ends, merged with a gap of the same kind next to them. */
+typedef struct { int pattern_begin_free, pattern_end_free, text_begin_free, text_end_free; } wfagpu_amd_span_t;
+
+/* wfagpu_amd_align_device with a span, exact search (NULL: end to end, identical to wfagpu_amd_align_device with BAND_NONE;
+ * all zero: the same results through the ends-free kernels).  Negative members: -1.
+ *   d_ends   optional device int32[2 * num_pairs] = {start diagonal k0, end diagonal k1} per pair (diagonal = text
+ *            position - pattern position).  The alignment starts at (pattern, text) = (max(-k0, 0), max(k0, 0)); with
+ *            kend = text_len - pattern_len, k1 >= kend means it used up the text with k1 - kend pattern bases left, k1 < kend
+ *            that it used up the pattern with kend - k1 text bases left.  k0 is found by the backtrace: score-only
+ *            calls leave INT32_MIN there. */
+int wfagpu_amd_align_device_span(wfagpu_amd_ctx_t* ctx, const wfagpu_amd_batch_t* batch, affine_penalties_t penalties, int max_error,
+                                 const wfagpu_amd_span_t* span, bool compute_cigar, int32_t* d_scores, int32_t* d_ends,
+                                 const char** d_text, const unsigned long long** d_off, const unsigned int** d_len);
+
+/* Process-wide, like wfagpu_amd_configure_launch: launch_alignments*, wfagpu_align and the CLI align under this span (exact
+ * search: a band that is asked for under a span is not used, said once on stderr).
+ * NULL: end to end.  Negative members: rejected (-1, message), state unchanged. */
+int wfagpu_amd_configure_span(const wfagpu_amd_span_t* span);
+
 void wfagpu_amd_last_stats(const wfagpu_amd_ctx_t* ctx, wfagpu_amd_stats_t* out);
 
 /* on = 1: the following calls on ctx align batches drawn from the same stream of reads (the batches of one

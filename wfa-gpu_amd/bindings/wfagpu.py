@@ -77,6 +77,11 @@ class Batch(C.Structure):  # wfagpu_amd_batch_t
                 ("d_packed", C.c_void_p)]
 
 
+class Span(C.Structure):  # wfagpu_amd_span_t: ends-free alignment, bases that may stay unaligned at no cost
+    _fields_ = [("pattern_begin_free", C.c_int), ("pattern_end_free", C.c_int), ("text_begin_free", C.c_int),
+                ("text_end_free", C.c_int)]
+
+
 class Stats(C.Structure):  # wfagpu_amd_stats_t
     _fields_ = [("pack_ms", C.c_float), ("align_ms", C.c_float), ("trace_ms", C.c_float), ("total_ms", C.c_float),
                 ("align_launches", C.c_int), ("cells", C.c_ulonglong), ("arena_units", C.c_ulonglong),
@@ -101,6 +106,7 @@ ABI_SYMBOLS = [
     "wfagpu_amd_last_launch_stats", "wfagpu_amd_set_tuning", "wfagpu_amd_stream", "wfagpu_amd_trim", "wfagpu_amd_prime",
     "wfagpu_amd_warmup", "wfagpu_amd_warmup_wait", "wfagpu_amd_last_launch_stats_device", "wfagpu_amd_debug_times",
     "wfagpu_host_pack_sequence", "wfagpu_host_pack_sequence_scalar", "wfagpu_host_pack_strip",
+    "wfagpu_amd_align_device_span", "wfagpu_amd_configure_span",
 ]
 
 _lib = None
@@ -133,6 +139,12 @@ def load():
                                             C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                             C.POINTER(C.c_void_p)]
     lib.wfagpu_amd_align_device.restype = C.c_int
+    lib.wfagpu_amd_align_device_span.argtypes = [C.c_void_p, C.POINTER(Batch), Penalties, C.c_int, C.POINTER(Span), C.c_bool,
+                                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                 C.POINTER(C.c_void_p)]
+    lib.wfagpu_amd_align_device_span.restype = C.c_int
+    lib.wfagpu_amd_configure_span.argtypes = [C.POINTER(Span)]
+    lib.wfagpu_amd_configure_span.restype = C.c_int
     lib.wfagpu_amd_last_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     lib.wfagpu_amd_last_stats.restype = None
     lib.wfagpu_amd_set_num_devices.argtypes = [C.c_int]
@@ -185,6 +197,25 @@ def configure_launch(**kw):
     tuning = Tuning(**kw.pop("tuning", {}))
     cfg = LaunchConfig(tuning=tuning, **kw)
     lib.wfagpu_amd_configure_launch(C.byref(cfg))
+
+
+def _as_span(span):
+    if span is None or isinstance(span, Span):
+        return span
+    if isinstance(span, dict):
+        return Span(**span)
+    return Span(*[int(v) for v in span])      # (pattern_begin_free, pattern_end_free, text_begin_free, text_end_free)
+
+
+def configure_span(**kw):
+    """wfagpu_amd_configure_span: launch_alignments*, wfagpu_align and the CLI align under this span (keyword arguments are the
+    fields of wfagpu_amd_span_t, missing ones 0).  No arguments: end to end again.  Raises ValueError on a negative member."""
+    lib = load()
+    if not kw:
+        lib.wfagpu_amd_configure_span(None)
+        return
+    if lib.wfagpu_amd_configure_span(C.byref(Span(**kw))) != 0:
+        raise ValueError(f"wfagpu_amd_configure_span rejected {kw}")
 
 
 def last_launch_stats():
@@ -444,10 +475,14 @@ class DeviceAligner:
             raise RuntimeError(f"wfagpu_amd_pack_device failed ({rc})")
         return d_packed.cpu().numpy().view(np.uint32), d_flags.cpu().numpy()
 
-    def align(self, batch, penalties, max_error, compute_cigar, band=-1, band_width=0, fetch=True, d_scores=None):
+    def align(self, batch, penalties, max_error, compute_cigar, band=-1, band_width=0, fetch=True, d_scores=None, span=None,
+              fetch_ends=False):
         """Returns (scores ndarray, cigars list or None).  With fetch=False results stay on the device
         and (d_scores tensor, (text_ptr, off_ptr, len_ptr)) is returned.  d_scores: the caller's int32 device tensor for the scores
-        (the C interface takes the caller's buffer: a loop of calls need not allocate one per call)."""
+        (the C interface takes the caller's buffer: a loop of calls need not allocate one per call).
+        span: a Span, a dict of its fields or a 4-tuple (pattern begin, pattern end, text begin, text end free): ends-free alignment
+        (wfagpu_amd_align_device_span; exact search, a band is an error).  fetch_ends (span only): a third result, int32[n, 2] =
+        the start and end diagonals (k0, k1) of every pair (k0 is INT32_MIN in score-only calls)."""
         torch = self.torch
         dev = torch.device("cuda", self.device)
         n = batch.num_pairs
@@ -456,19 +491,36 @@ class DeviceAligner:
         assert d_scores.dtype == torch.int32 and d_scores.numel() >= max(n, 1) and d_scores.is_cuda
         t, o, l = C.c_void_p(), C.c_void_p(), C.c_void_p()
         pen = Penalties(*penalties)
+        span = _as_span(span)
+        d_ends = None
+        if span is not None:
+            if band > 0 and band_width > 0:
+                raise ValueError("the adaptive band is not combined with an ends-free span")
+            if fetch_ends:
+                d_ends = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev)
+        elif fetch_ends:
+            raise ValueError("fetch_ends needs a span")
         self._inputs_ready()
-        rc = self.lib.wfagpu_amd_align_device(self.ctx, C.byref(batch), pen, int(max_error), int(band), int(band_width),
-                                              bool(compute_cigar), d_scores.data_ptr(), C.byref(t), C.byref(o),
-                                              C.byref(l))
+        if span is not None:
+            rc = self.lib.wfagpu_amd_align_device_span(self.ctx, C.byref(batch), pen, int(max_error), C.byref(span), bool(compute_cigar),
+                                                       d_scores.data_ptr(), d_ends.data_ptr() if d_ends is not None else None,
+                                                       C.byref(t), C.byref(o), C.byref(l))
+        else:
+            rc = self.lib.wfagpu_amd_align_device(self.ctx, C.byref(batch), pen, int(max_error), int(band), int(band_width),
+                                                  bool(compute_cigar), d_scores.data_ptr(), C.byref(t), C.byref(o),
+                                                  C.byref(l))
         if rc != 0:
-            raise RuntimeError(f"wfagpu_amd_align_device failed ({rc})")
+            raise RuntimeError(f"wfagpu_amd_align_device{'_span' if span is not None else ''} failed ({rc})")
         if not fetch:
-            return d_scores[:n], (t.value, o.value, l.value)
+            res = (d_scores[:n], (t.value, o.value, l.value))
+            return res + (d_ends[:n],) if fetch_ends else res
         scores = d_scores[:n].cpu().numpy()
         cigars = None
         if compute_cigar and n:
             st = self.stats()
             cigars = fetch_cigars(t.value, o.value, l.value, n, st.text_bytes)
+        if fetch_ends:
+            return scores, cigars, d_ends[:n].cpu().numpy()
         return scores, cigars
 
     def stats(self):

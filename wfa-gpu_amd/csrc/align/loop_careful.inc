@@ -2,6 +2,9 @@
 // Textually included in the body of wfa_align_kernel (../align_kernel.hip), where every name used here is declared.
 // One iteration of the score loop: every score of the byte-compare and 32-bit tiers after the first touch, the last few scores of every alignment.
         ++s;
+        // (ENDSFREE: the reach interval surrounds an interval of end diagonals and outlives the budget by some scores: said here, the row
+        // table holds the scores up to the budget)
+        if constexpr (ENDSFREE) { if (s > budget) { status = WFA_ST_SCORE; break; } }
         // (past the budget the reach interval is empty, so that test sits on the "no wavefront" path)
         if (reach_r == 0) { ++rlo; --rhi; reach_r = e - 1; } else --reach_r;
         if constexpr (NW > 1) {
@@ -133,6 +136,23 @@
         bool my_over = false;
         unsigned long long touch_mask = 0;
         cells_of_score(std::false_type{}, lo, hi, codes, rb_mx, rb_mo, rb_ie, rb_de, wb_m, wb_i, wb_d, my_over, touch_mask);
+        // (ENDSFREE) termination (wavefront_extend.c:124-170, 240-262): the LOWEST diagonal of the extended M row whose cell has used up
+        // the text with at most pef pattern bases left, or the pattern with at most tef text bases left.  Every wave scans the cells it
+        // has just written (same striping as cells_of_score, ascending: its first hit is its lowest); NW > 1: the minimum over the waves
+        // through word 0 of the score's reduction slot, under the barrier the score has anyway.
+        int my_end = INT_MAX;
+        if constexpr (ENDSFREE) {
+          const int wave = (NW == 1) ? 0 : __builtin_amdgcn_readfirstlane(tid >> 6);
+          for (int k0 = lo; k0 <= hi; k0 += NT) {
+            const int kraw = k0 + tid;
+            const bool act = kraw <= hi;
+            const int k = act ? kraw : hi;
+            const int h = (int)wb_m[k], v = h - k;
+            const bool hit = act && h >= 0 && ((h >= tlen && plen - v <= pef) || (v >= plen && tlen - h <= tef));
+            const unsigned long long bh = __builtin_amdgcn_ballot_w64(hit);
+            if (bh) { my_end = k0 + wave * 64 + (int)__builtin_ctzll(bh); break; }
+          }
+        }
         bool any_over = false;
         {
           const bool wave_over = __builtin_amdgcn_ballot_w64(my_over) != 0ull;
@@ -141,15 +161,19 @@
             block_sync<NW>();
             any_over = wave_over;
             touched_ever |= wave_touch;
+            if constexpr (ENDSFREE) end_k = my_end;
           } else {
             int* acc = red + 8 * (s % 3);
             if (lane == 0 && (wave_over || wave_touch)) atomicOr(&acc[6], (wave_over ? 2 : 0) | (wave_touch ? 4 : 0));
+            if constexpr (ENDSFREE) { if (lane == 0 && my_end != INT_MAX) atomicMin(&acc[0], my_end); }
             __syncthreads();
             any_over = (acc[6] & 2) != 0;
             touched_ever |= (acc[6] & 4) != 0;
+            if constexpr (ENDSFREE) end_k = acc[0];
           }
           // termination (wavefront_extend.c:47-67): every lane reads the same cell
-          done = ((unsigned)(kend - lo) <= (unsigned)(hi - lo)) && __builtin_amdgcn_readfirstlane((int)wb_m[kend]) >= tlen;
+          if constexpr (ENDSFREE) done = end_k != INT_MAX;
+          else done = ((unsigned)(kend - lo) <= (unsigned)(hi - lo)) && __builtin_amdgcn_readfirstlane((int)wb_m[kend]) >= tlen;
         }
         // Limits recorded for the row: the computed ones.  Cells that are not valid hold NULL or a
         // negative value, which is all a reader needs; only values past a sequence end need the

@@ -19,7 +19,7 @@
         // backtrace only ever visits valid cells, and a NULL never equals a run limit (no false "touched").  Same argument as the
         // e == 1 loop's, which computes [-s, s]; SURVEY.md A.1.  A score WFA2 has no wavefront for is a row of NULL cells here.
         // The interval grows by one diagonal a side every e scores (one counter), the reach interval shrinks alike (reach_r).
-        if constexpr (HOT && !BANDED) {
+        if constexpr (HOT && !BANDED && !ENDSFREE) {
           if (e != 1 && !touched_ever) {
             const int s_in = s;
             const int o_pen = oe - e;

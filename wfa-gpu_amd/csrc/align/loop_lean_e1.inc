@@ -17,7 +17,7 @@
         // (every neighbour is a non-negative immediate away), row book written when the loop is left (its entries are
         // a function of the score), row-table entries by v_writelane, guard cells re-NULLed only once the budget's
         // reach makes the wavefront shrink (a growing wavefront overwrites everything its slot held before).
-        if constexpr (HOT && !BANDED) {
+        if constexpr (HOT && !BANDED && !ENDSFREE) {
           if (e == 1 && !touched_ever) {
             const int s_in = s, lo_in = last_lo, hi_in = last_hi;
             // lo(s) = max(lo_in - (s - s_in), wlo, s + c_lo), hi(s) = min(hi_in + (s - s_in), whi, c_hi - s)

@@ -1,7 +1,7 @@
 // loop_lean_hbm.inc -- lean score loop of the tiers whose ring lives in HBM (tier 3: 16- or 32-bit offsets through L2).
 // Textually included in the body of wfa_align_kernel (../align_kernel.hip), where every name used here is declared.
 // Same contract as the other lean loops, generic cells (cells_of_score<LEAN>).
-        if constexpr (!HOT) {
+        if constexpr (!HOT && !ENDSFREE) {
           // (the tiers whose ring lives in HBM: one loop for every gap extension -- they are bound by the ring traffic, a
           // closed-form e == 1 twin of it bought nothing there)
           if (!touched_ever) {

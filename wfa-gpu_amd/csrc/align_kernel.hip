@@ -178,10 +178,15 @@ __device__ __forceinline__ ColdParams cold_params() {
 // that matches the rings a CU holds (plan_tier).
 // TIMED (diagnostics, tuning.timed_barriers): workgroup 0 records, for every score of the closed-form lean loop, the s_memtime
 // at which each of its waves reaches the per-score barrier and the one at which it leaves it (profiles/r04/barrier_skew.md).
-template <int NW, bool BT, typename OffT, bool GLOBAL_RING, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool TIMED = false>
+// ENDSFREE (align_kernel_ef.hip includes this file for those instantiations): the alignment may start anywhere on the free part of
+// the first row / column and end anywhere on the free part of the last ones (WFA2's alignment_endsfree).  Score 0 is a row of
+// diagonals, every score's extended M row is scanned for the lowest diagonal that satisfies WFA2's termination, the diagonal it
+// ended on goes to WfaAlignParams::ends; careful loop only, origin bytes in ROWS.  Everything else is the end-to-end kernel.
+template <int NW, bool BT, typename OffT, bool GLOBAL_RING, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool TIMED = false, bool ENDSFREE = false>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu((NW == 1 && !BANDED) ? WPE : 1, 8)))
 wfa_align_kernel(const WfaAlignParams p) {
   static_assert(!HYBRID || (!GLOBAL_RING && !BANDED), "the hybrid ring is an exact LDS tier");
+  static_assert(!ENDSFREE || (!BANDED && !HYBRID && !TIMED), "ends-free: the exact search of tiers 0, 1, 2 and 3");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NT = NW * 64;
   const int tid = threadIdx.x;
@@ -208,7 +213,7 @@ wfa_align_kernel(const WfaAlignParams p) {
   // of one bump-allocated row per score behind a row table (wfa_device.h).  The backward walk of a 1 kbp alignment then touches ~35
   // cache lines instead of 74 (55 origin bytes on 55 lines + 19 lines of row table: wfa_walk_kernel is bound by random 64-byte
   // accesses), and a score of the lean loops neither sizes, claims nor records a row: no refill test, no row-table entry.
-  constexpr bool TILED = BT && HOT && !HYBRID && NW == 1 && !BANDED;
+  constexpr bool TILED = BT && HOT && !HYBRID && NW == 1 && !BANDED && !ENDSFREE;      // (ends-free: ROWS in every tier)
   const int GZ = BANDED ? 4 * dm + 2 : 0;
   const int x = p.x, oe = p.oe, e = p.e;
 
@@ -285,6 +290,13 @@ wfa_align_kernel(const WfaAlignParams p) {
     const WfaSeqPair mp = cold_params()->meta[pair];
     const int plen = __builtin_amdgcn_readfirstlane((int)mp.pattern_len), tlen = __builtin_amdgcn_readfirstlane((int)mp.text_len);
     const int kend = tlen - plen;
+    // (ENDSFREE) the span of this pair: each value clamped to its sequence's length
+    int pbf = 0, pef = 0, tbf = 0, tef = 0;
+    if constexpr (ENDSFREE) {
+      ColdParams cp = cold_params();
+      pbf = min(cp->span_pbf, plen); pef = min(cp->span_pef, plen); tbf = min(cp->span_tbf, tlen); tef = min(cp->span_tef, tlen);
+    }
+    int end_k = INT_MAX;                    // (ENDSFREE) the diagonal the alignment ended on
     const int pwords = RAW ? ((plen + 3) >> 2) + 1 : ((plen + 15) >> 4) + 1;
     const int twords = RAW ? ((tlen + 3) >> 2) + 1 : ((tlen + 15) >> 4) + 1;
 
@@ -312,7 +324,23 @@ wfa_align_kernel(const WfaAlignParams p) {
     }
     int wlo = -plen, whi = tlen;
     bool feasible = true;
-    {
+    if constexpr (ENDSFREE) {
+      // Ends-free: a path starts on a diagonal a of S = [-pbf, tbf] and ends on a diagonal b of E = [kend - tef, kend + pef].  One that
+      // visits k above both needs k - a bases of insertion and k - b of deletion in at least one gap each: 2o + (2k - a - b) e, largest
+      // reach at a = tbf, b = kend + pef; below both, symmetric.  Between the hulls' ends every diagonal stays.  With a span of zeros
+      // these are the end-to-end formulas.  feasible: the gap between the two intervals is affordable.
+      const int s_lo = -pbf, s_hi = tbf, e_lo = kend - tef, e_hi = kend + pef;
+      const int H = max(s_hi, e_hi), L = min(s_lo, e_lo);
+      if (budget < INT_MAX / 2) {
+        const long long S = budget, o = oe - e;
+        const int gap = max(0, max(e_lo - s_hi, s_lo - e_hi));
+        feasible = (gap ? o + (long long)gap * e : 0) <= S;
+        const long long a_hi = S - 2 * o + ((long long)s_hi + e_hi) * e, a_lo = S - 2 * o - ((long long)s_lo + e_lo) * e;
+        whi = a_hi >= 0 ? max(H, (int)min((long long)tlen, a_hi / (2 * e))) : H;
+        wlo = a_lo >= 0 ? min(L, -(int)min((long long)plen, a_lo / (2 * e))) : L;
+        whi = min(whi, tlen); wlo = max(wlo, -plen);
+      }
+    } else {
       if (budget < INT_MAX / 2) {
         const long long S = budget, o = oe - e;
         const int ak = kend < 0 ? -kend : kend;
@@ -450,7 +478,41 @@ wfa_align_kernel(const WfaAlignParams p) {
       auto tile_row = [&](const int sc) -> GlobalBytes { return tiles0 + ((size_t)((uint32_t)sc >> 2) * tile_cols * 64u + ((uint32_t)sc & 3u) * 16u); };
       auto tile_off = [&](const int kk) -> uint32_t { const uint32_t d = (uint32_t)(kk - wlo); return d + 3u * (d & ~15u); };
       uint32_t d0 = 0;
-      if (tid == 0) {
+      if constexpr (ENDSFREE) {
+        // Score 0 (wavefront_unialign.c:137-178): M on every diagonal of [-pbf, tbf] at offset max(k, 0), each extended; striped over the
+        // lanes like any row.  The termination scan of a row (loop_careful.inc) for this one: the lowest diagonal that satisfies it.
+        constexpr int SH = RAW ? 2 : 4, PER = 1 << SH, BITS = RAW ? 3 : 1;
+        OffT* const row0 = Mr + kidx0;
+        const int wave = (NW == 1) ? 0 : __builtin_amdgcn_readfirstlane(tid >> 6);
+        for (int k0 = -pbf; k0 <= tbf && end_k == INT_MAX; k0 += NT) {
+          const int k = k0 + tid;
+          const bool act = k <= tbf;
+          int h = max(k, 0), v = h - k;
+          int rem = act ? min(plen - v, tlen - h) : 0;
+          while (rem > 0) {
+            const uint32_t* pw = Pw + (v >> SH); const uint32_t* tw = Tw + (h >> SH);
+            const uint32_t d = __builtin_amdgcn_alignbit(pw[1], pw[0], (uint32_t)(v & (PER - 1)) << BITS) ^
+                               __builtin_amdgcn_alignbit(tw[1], tw[0], (uint32_t)(h & (PER - 1)) << BITS);
+            const int n = min(d ? (int)((uint32_t)__builtin_ctz(d) >> BITS) : PER, rem);
+            h += n; v += n; rem -= n;
+            if (n < PER) break;
+          }
+          if (act) row0[k] = (OffT)h;
+          const bool hit = act && ((h >= tlen && plen - v <= pef) || (v >= plen && tlen - h <= tef));
+          const unsigned long long bh = __builtin_amdgcn_ballot_w64(hit);
+          if (bh) end_k = k0 + wave * 64 + (int)__builtin_ctzll(bh);
+        }
+        if constexpr (NW > 1) {
+          // (word 0 of reduction slot 0: INT_MAX since the reset above, initialised again by score 2)
+          if (lane == 0 && end_k != INT_MAX) atomicMin(&red[0], end_k);
+          __syncthreads();
+          end_k = red[0];
+        }
+        ncells = (uint32_t)(pbf + tbf + 1);
+        book.set(0, pack_range(-pbf, tbf), ROW_NONE_A, ROW_NONE_A);
+        done = end_k != INT_MAX;
+      }
+      if (!ENDSFREE && tid == 0) {
         // longest common prefix from (0,0): both sequences start word-aligned
         constexpr int SH = RAW ? 2 : 4, PER = 1 << SH, BITS = RAW ? 3 : 1;
         int h0 = 0, rem = min(plen, tlen);
@@ -463,9 +525,11 @@ wfa_align_kernel(const WfaAlignParams p) {
         Mr[kidx0 + GZ] = (OffT)h0;      // (banded: the row of score 0 has lo = 0)
         d0 = ((kend == 0 && h0 >= tlen) ? 1u : 0u) | (h0 >= min(plen, tlen) ? 2u : 0u);
       }
-      book.set(0, pack_range(0, 0), ROW_NONE_A, ROW_NONE_A);
-      d0 = block_bcast<NW>(d0, bslot);
-      done = (d0 & 1u) != 0;
+      if constexpr (!ENDSFREE) {
+        book.set(0, pack_range(0, 0), ROW_NONE_A, ROW_NONE_A);
+        d0 = block_bcast<NW>(d0, bslot);
+        done = (d0 & 1u) != 0;
+      }
       const bool touched_at_0 = (d0 & 2u) != 0;
       block_sync<NW>();
 
@@ -489,7 +553,8 @@ wfa_align_kernel(const WfaAlignParams p) {
       // drops, tracked through the remainder reach_r without a division per score.
       const bool bounded = budget < INT_MAX / 2;
       int reach_r = bounded ? budget % e : INT_MAX;
-      int rlo = bounded ? kend - budget / e : INT_MIN / 2, rhi = bounded ? kend + budget / e : INT_MAX / 2;
+      // (ENDSFREE: around the interval of end diagonals [kend - tef, kend + pef])
+      int rlo = bounded ? kend - tef - budget / e : INT_MIN / 2, rhi = bounded ? kend + pef + budget / e : INT_MAX / 2;
       // Number of consecutive scores up to s-1 whose wavefront exists with all three components and
       // untrimmed limits.  Once that covers every row the recurrences read, the limits follow from the M
       // limits alone and none of the "no wavefront" cases of wavefront_compute.c:41-71 can occur.
@@ -534,7 +599,8 @@ wfa_align_kernel(const WfaAlignParams p) {
       // I or D value run past a sequence end (every such value has a predecessor chain that starts at an M cell sitting
       // on the border), and only such a cell can be the final one.  Until then the lean path needs neither the
       // per-cell overrun tests nor the per-score termination read.
-      bool touched_ever = touched_at_0 || cold_params()->no_lean != 0;    // (WFAGPU_NO_LEAN: the lean path is never entered)
+      // (ENDSFREE: the careful loop only -- a row of score 0 that starts on the borders has touched them)
+      bool touched_ever = ENDSFREE || touched_at_0 || cold_params()->no_lean != 0;    // (WFAGPU_NO_LEAN: the lean path is never entered)
       // ---- score loop ----------------------------------------------------------------------------
       if (!done && status == WFA_ST_DONE) for (;;) {
         #include "align/loop_banded.inc"
@@ -551,6 +617,10 @@ wfa_align_kernel(const WfaAlignParams p) {
         }
       }
     }
+    if constexpr (ENDSFREE) {
+      // the diagonal the alignment ended on; the one it started on is the backtrace's to find
+      if (tid == 0 && status == WFA_ST_DONE) { int32_t* const en = cold_params()->ends + 2 * (size_t)pair; en[0] = INT_MIN; en[1] = end_k; }
+    }
     if (tid == 0) {
       ColdParams cp = cold_params();
       cp->score[pair] = (status == WFA_ST_DONE) ? s : -1;
@@ -566,9 +636,9 @@ wfa_align_kernel(const WfaAlignParams p) {
   }
 }
 
-template <int NW, bool BT, typename OffT, bool GR, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool TIMED = false>
+template <int NW, bool BT, typename OffT, bool GR, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool TIMED = false, bool EF = false>
 void launch_inst(const WfaAlignParams& p, size_t lds, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
-  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE, TIMED>;
+  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE, TIMED, EF>;
   // the opt-in for large dynamic LDS is sticky per device and per kernel: pay the driver call once
   static thread_local size_t allowed[16] = {0};
   int dev = 0;
@@ -580,9 +650,9 @@ void launch_inst(const WfaAlignParams& p, size_t lds, int grid, hipStream_t stre
   wfa_launch_timed(k, dim3(grid), dim3(NW * 64), lds, stream, ev0, ev1, p);
 }
 
-template <int NW, bool BT, typename OffT, bool GR, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8>
+template <int NW, bool BT, typename OffT, bool GR, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool EF = false>
 int occ_inst(size_t lds) {
-  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE>;
+  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE, false, EF>;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   int nb = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), NW * 64, lds) != hipSuccess) {
@@ -592,6 +662,47 @@ int occ_inst(size_t lds) {
   return nb;
 }
 
+#ifdef WFA_ALIGN_ENDSFREE_UNIT
+// ---- the ends-free translation unit (align_kernel_ef.hip): tiers 0, 1, 2 and 3, with and without backtrace, packed and byte-compare
+template <bool BT, bool RAW>
+void launch_tier_ef(const WfaAlignParams& p, int tier, size_t lds, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  switch (tier) {
+    case 0: launch_inst<1, BT, int16_t, false, RAW, false, false, 8, false, true>(p, lds, grid, stream, ev0, ev1); break;
+    case 1: launch_inst<4, BT, int16_t, false, RAW, false, false, 8, false, true>(p, lds, grid, stream, ev0, ev1); break;
+    case 2: launch_inst<16, BT, int16_t, false, RAW, false, false, 8, false, true>(p, lds, grid, stream, ev0, ev1); break;
+    default:
+      if (p.ring16) launch_inst<16, BT, int16_t, true, RAW, false, false, 8, false, true>(p, lds, grid, stream, ev0, ev1);
+      else launch_inst<16, BT, int32_t, true, RAW, false, false, 8, false, true>(p, lds, grid, stream, ev0, ev1);
+      break;
+  }
+}
+template <bool BT, bool RAW>
+int occ_tier_ef(int tier, size_t lds) {
+  switch (tier) {
+    case 0: return occ_inst<1, BT, int16_t, false, RAW, false, false, 8, true>(lds);
+    case 1: return occ_inst<4, BT, int16_t, false, RAW, false, false, 8, true>(lds);
+    case 2: return occ_inst<16, BT, int16_t, false, RAW, false, false, 8, true>(lds);
+    default: return occ_inst<16, BT, int32_t, true, RAW, false, false, 8, true>(lds);
+  }
+}
+
+}  // namespace
+
+void wfa_launch_align_ef(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  const size_t lds = wfa_align_lds_bytes(p, tier);
+  if (with_bt) { if (raw) launch_tier_ef<true, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_ef<true, false>(p, tier, lds, grid, stream, ev0, ev1); }
+  else { if (raw) launch_tier_ef<false, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_ef<false, false>(p, tier, lds, grid, stream, ev0, ev1); }
+}
+
+int wfa_align_ef_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds) {
+  if (with_bt) return raw ? occ_tier_ef<true, true>(tier, lds) : occ_tier_ef<true, false>(tier, lds);
+  return raw ? occ_tier_ef<false, true>(tier, lds) : occ_tier_ef<false, false>(tier, lds);
+}
+
+// (this code object is loaded by the first launch of one of its kernels: wfagpu_amd_prime does that only under a configured span)
+namespace { __global__ void k_prime_align_ef() {} }
+void wfa_prime_align_ef(hipStream_t stream) { hipLaunchKernelGGL(k_prime_align_ef, dim3(1), dim3(64), 0, stream); }
+#else
 // tier -> instantiation (banded kernels exist for the packed LDS tiers only)
 template <bool BT, bool RAW>
 void launch_tier(const WfaAlignParams& p, int tier, size_t lds, int grid, hipStream_t stream, int wpe, hipEvent_t ev0, hipEvent_t ev1) {
@@ -693,3 +804,4 @@ int wfa_align_max_blocks_per_cu(int tier, bool with_bt, bool raw, bool banded, s
 // any of its kernels: 5-25 ms each): launch_alignments* call it while a cold call waits for its first upload.
 namespace { __global__ void k_prime_align() {} }
 void wfa_prime_align(hipStream_t stream) { hipLaunchKernelGGL(k_prime_align, dim3(1), dim3(64), 0, stream); }
+#endif      // WFA_ALIGN_ENDSFREE_UNIT

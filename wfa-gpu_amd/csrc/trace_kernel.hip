@@ -139,6 +139,10 @@ __device__ __forceinline__ int dec_digits(uint32_t n) {
          n < 100000000 ? 8 : n < 1000000000 ? 9 : 10;
 }
 
+// The diagonals an alignment starts and ends on.  End to end: 0 and tlen - plen.  Ends-free (WfaTraceParams::ends): k1 comes from the
+// wavefront kernel, k0 is where the walk arrives.
+struct PairEnds { int k0, k1; };
+
 struct RleSink {
   char* out;      // nullptr: count only
   uint32_t cap;   // bytes available at `out` (items that would not fit are only counted)
@@ -148,6 +152,7 @@ struct RleSink {
   int x, o, e;    // penalties: the gap-affine cost of the emitted items is accumulated while writing
   int cost;
   bool words;     // the slot at `out` is this lane's own up to `cap`: an item may be stored as one (unaligned) 32-bit word
+  uint32_t free_run;   // bases of the current run that are free (ends-free alignment): printed, not priced
   __device__ __forceinline__ void flush() {
     if (run == 0) return;
     const int nd = dec_digits(run);
@@ -166,25 +171,33 @@ struct RleSink {
       }
     }
     // (utils/verification.c:91-146 of the reference: a new gap wherever the operation changes)
+    // (a free run merges with a paid gap of the same kind next to it: the gap is priced for its paid bases alone)
     if (op == 'X') cost += x * (int)run;
-    else if (op != 'M') cost += o + e * (int)run;
+    else if (op != 'M' && run > free_run) cost += o + e * (int)(run - free_run);
     len += (uint32_t)nd + 1;
-    run = 0;
+    run = 0; free_run = 0;
   }
   __device__ __forceinline__ void push(char o, uint32_t n) {
     if (n == 0) return;
     if (o != op) { flush(); op = o; }
     run += n;
   }
+  __device__ __forceinline__ void push_free(char o, uint32_t n) {
+    if (n == 0) return;
+    push(o, n);
+    free_run += n;
+  }
 };
 
 // (OPS_LDS: the op list is in LDS -- said explicitly, a pointer that was global or LDS by a run-time choice loads with flat_load)
 template <bool RAW, bool OPS_LDS = false, typename PV, typename TV>
 __device__ __forceinline__ uint32_t replay_views(const uint8_t* ops, uint32_t nops, PV& Pw, TV& Tw,
-                                                 int plen, int tlen, char* out, int x, int o, int e, int* cost,
+                                                 int plen, int tlen, const PairEnds ends, char* out, int x, int o, int e, int* cost,
                                                  uint32_t out_cap = 0xFFFFFFFFu, bool words = false) {
-  RleSink sink{out, out_cap, 0, 0, 0, x, o, e, 0, words};
-  int v = 0, h = 0;
+  RleSink sink{out, out_cap, 0, 0, 0, x, o, e, 0, words, 0};
+  // (ends-free: the path starts on diagonal k0 at the border, behind the free bases of the sequence that sticks out)
+  int v = max(-ends.k0, 0), h = max(ends.k0, 0);
+  sink.push_free(ends.k0 > 0 ? 'I' : 'D', (uint32_t)(v + h));
   int n = lcp_seq<RAW>(Pw, Tw, plen, tlen, v, h);
   sink.push('M', (uint32_t)n); v += n; h += n;
   // The op list is consumed four ops per aligned 32-bit load: with one byte load per step every iteration of every lane
@@ -211,19 +224,22 @@ __device__ __forceinline__ uint32_t replay_views(const uint8_t* ops, uint32_t no
       sink.push('M', (uint32_t)n); v += n; h += n;
     }
   }
+  // a consistent trace ends on diagonal k1 with one sequence used up (end to end: exactly at the corner); what is left of the other
+  // one is free
+  const bool at_end = (h - v == ends.k1) && (v == plen || h == tlen);
+  if (at_end) { sink.push_free('D', (uint32_t)(plen - v)); sink.push_free('I', (uint32_t)(tlen - h)); }
   sink.flush();
   if (out && sink.len < out_cap) out[sink.len] = '\0';
   if (cost) *cost = sink.cost;
-  // a consistent trace ends exactly at the corner
-  return (v == plen && h == tlen) ? sink.len : 0xFFFFFFFFu;
+  return at_end ? sink.len : 0xFFFFFFFFu;
 }
 
 template <bool RAW, bool OPS_LDS = false>
 __device__ __forceinline__ uint32_t replay(const uint8_t* ops, uint32_t nops, const uint32_t* Pw, const uint32_t* Tw,
-                                           int plen, int tlen, char* out, int x, int o, int e, int* cost,
+                                           int plen, int tlen, const PairEnds ends, char* out, int x, int o, int e, int* cost,
                                            uint32_t out_cap = 0xFFFFFFFFu, bool words = false) {
   SeqDirect pv{Pw}, tv{Tw};
-  return replay_views<RAW, OPS_LDS>(ops, nops, pv, tv, plen, tlen, out, x, o, e, cost, out_cap, words);
+  return replay_views<RAW, OPS_LDS>(ops, nops, pv, tv, plen, tlen, ends, out, x, o, e, cost, out_cap, words);
 }
 
 constexpr int TRACE_THREADS = 64;
@@ -293,8 +309,22 @@ __device__ __forceinline__ uint32_t walk_step(const uint32_t code, int& state, i
   }
   return op;
 }
-// a consistent walk ends in M at (0, 0)
-__device__ __forceinline__ bool walk_ended(const int s, const int state, const int k) { return s == 0 && state == 0 && k == 0; }
+// The span of a walk: it starts on diagonal k1 and may end on any diagonal of [k0_lo, k0_hi] (end to end: on tlen - plen and on 0).
+struct WalkSpan { int k1, k0_lo, k0_hi; };
+__device__ __forceinline__ WalkSpan walk_span(const WfaTraceParams& p, const size_t pair, const int plen, const int tlen) {
+  WalkSpan w;
+  w.k1 = p.ends ? p.ends[2 * pair + 1] : tlen - plen;
+  w.k0_lo = -min(p.span_pbf, plen); w.k0_hi = min(p.span_tbf, tlen);
+  return w;
+}
+// a consistent walk ends in M at score 0 on a diagonal the alignment may start on ((0, 0) end to end)
+__device__ __forceinline__ bool walk_ended(const int s, const int state, const int k, const WalkSpan& w) { return s == 0 && state == 0 && k >= w.k0_lo && k <= w.k0_hi; }
+// what the replay starts from and must arrive at: the walk's result (kernels that walk and replay), or the stored one
+__device__ __forceinline__ PairEnds stored_ends(const WfaTraceParams& p, const size_t pair, const int plen, const int tlen) {
+  PairEnds e{0, tlen - plen};
+  if (p.ends) { e.k0 = p.ends[2 * pair]; e.k1 = p.ends[2 * pair + 1]; }
+  return e;
+}
 
 // One 64-byte line -> the lane's cache slot in LDS.
 __device__ __forceinline__ void cache_line(const void* line, uint2* const slot) {
@@ -310,14 +340,15 @@ __device__ __forceinline__ void cache_line(const void* line, uint2* const slot) 
 // as a byte list that grows downwards from q_end (op number n, 0 = last operation of the alignment, is byte q_end[-1-n]; q_end is
 // 4-byte aligned, four ops go out as one word).  tab_cache: this lane's 8 row-table entries of LDS.  false: broken trace.
 __device__ __forceinline__ bool walk_ops(const WfaTraceParams& p, const uint32_t pair, const int score, const int plen, const int tlen,
-                                         uint8_t* const q_end, const uint32_t need_ops, uint2* const tab_cache_lane, uint32_t& nops_out) {
+                                         uint8_t* const q_end, const uint32_t need_ops, uint2* const tab_cache_lane, uint32_t& nops_out, PairEnds& ends_out) {
   bool fail = false;
   uint32_t nops = 0, word = 0;
   // (tiles: no table to consult, and the ~55 origin bytes of a 1 kbp alignment sit on ~35 cache lines instead of 55 + 19 lines of
   // row table)
   const BtBlock bb = bt_block(p, pair);
   const uint2* tab = reinterpret_cast<const uint2*>(bb.blk);
-  int k = tlen - plen, s = score;
+  const WalkSpan span = walk_span(p, pair, plen, tlen);
+  int k = span.k1, s = score;
   int state = 0;  // 0: M, 1: I, 2: D
   int cached = -1;
   while (s > 0) {
@@ -343,7 +374,9 @@ __device__ __forceinline__ bool walk_ops(const WfaTraceParams& p, const uint32_t
     ++nops;
     if ((nops & 3u) == 0u) reinterpret_cast<uint32_t*>(q_end)[-(int)(nops >> 2)] = word;
   }
-  if (!walk_ended(s, state, k)) fail = true;
+  if (!walk_ended(s, state, k, span)) fail = true;
+  ends_out = PairEnds{k, span.k1};
+  if (!fail && p.ends) p.ends[2 * (size_t)pair] = k;      // (the start diagonal: the caller's, and the replay kernel's)
   if (!fail && (nops & 3u)) {
     // the last, partial word: its ops are the first operations of the alignment
     uint8_t* qq = q_end - (nops & ~3u);
@@ -434,7 +467,8 @@ __global__ void __launch_bounds__(WALK_WAVES * 64) wfa_walk_kernel(const WfaTrac
     uint8_t* const q_begin = p.ops + ops_off;
     uint8_t* const q_end = q_begin + need_ops;       // (4-byte aligned: the allocations are multiples of 4)
     uint32_t nops = 0;
-    if (active && !fail) fail = !walk_ops(p, pair, score, plen, tlen, q_end, need_ops, tab_cache[threadIdx.x], nops);
+    PairEnds ends;
+    if (active && !fail) fail = !walk_ops(p, pair, score, plen, tlen, q_end, need_ops, tab_cache[threadIdx.x], nops, ends);
     if (active) {
       // the op list now sits at [q_end - nops, q_end); cigar_off/cigar_len carry it to the emit kernel
       p.cigar_off[pair] = (unsigned long long)(q_end - nops - p.ops);
@@ -467,9 +501,10 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_win_kernel(const WfaTr
     nops = p.cigar_len[pair];
     fail = nops == 0xFFFFFFFFu;
   }
+  const PairEnds ends = stored_ends(p, pair, plen, tlen);
   uint32_t len = 0;
   if (active && !fail) {
-    len = replay_any(p.raw, q, nops, pv, tv, plen, tlen, (char*)nullptr, 0, 0, 0, (int*)nullptr);
+    len = replay_any(p.raw, q, nops, pv, tv, plen, tlen, ends, (char*)nullptr, 0, 0, 0, (int*)nullptr);
     if (len == 0xFFFFFFFFu) fail = true;
   }
   const uint32_t need_txt = (active && !fail) ? len + 1u : 0u;
@@ -479,7 +514,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_win_kernel(const WfaTr
     if (!fail) {
       int cost = 0;
       pv.base = -1000; tv.base = -1000;
-      replay_any(p.raw, q, nops, pv, tv, plen, tlen, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
+      replay_any(p.raw, q, nops, pv, tv, plen, tlen, ends, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
       finish_pair(p, pair, false, txt_off, len, cost, p.score[pair]);
     } else finish_pair(p, pair, true);
   }
@@ -562,11 +597,12 @@ __global__ void __launch_bounds__(LANE_WAVES * 64) wfa_trace_lane_kernel(const W
   bool fail = active && need_ops > (uint32_t)p.ops_lds_bytes;
   uint8_t* const q_end = ops_lds + (size_t)lane * p.ops_lds_bytes + need_ops;      // (the lane's slot: 4-byte aligned, like need_ops)
   uint32_t nops = 0;
-  if (active && !fail) fail = !walk_ops(p, pair, score, plen, tlen, q_end, need_ops, tab_cache + (size_t)lane * (LANE_CACHE_BYTES / 8), nops);
+  PairEnds ends{0, 0};
+  if (active && !fail) fail = !walk_ops(p, pair, score, plen, tlen, q_end, need_ops, tab_cache + (size_t)lane * (LANE_CACHE_BYTES / 8), nops, ends);
   const uint8_t* const q = q_end - nops;
   uint32_t len = 0;
   if (active && !fail) {
-    len = replay<RAW>(q, nops, Pw, Tw, plen, tlen, nullptr, 0, 0, 0, nullptr);
+    len = replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, nullptr, 0, 0, 0, nullptr);
     if (len == 0xFFFFFFFFu) fail = true;
   }
   const uint32_t need_txt = (active && !fail) ? len + 1u : 0u;
@@ -574,7 +610,7 @@ __global__ void __launch_bounds__(LANE_WAVES * 64) wfa_trace_lane_kernel(const W
   if (active && !fail && txt_off + need_txt > p.text_cap) fail = true;
   if (active) {
     int cost = 0;
-    if (!fail) replay<RAW>(q, nops, Pw, Tw, plen, tlen, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
+    if (!fail) replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
     finish_pair(p, pair, fail, txt_off, len, cost, score);
   }
 }
@@ -632,18 +668,19 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_kernel(const WfaTraceP
     q_lds = reinterpret_cast<const uint8_t*>(ops_l + (size_t)lane * lwords) + (reinterpret_cast<uintptr_t>(q) & 3);
   }
   SeqDirect pv{Pw}, tv{Tw};      // (the staged sequences, or the global ones)
+  const PairEnds ends = stored_ends(p, pair, plen, tlen);
   if (p.text_scratch) {
     // single replay: the text goes to this lane's slot of the scratch (sized by the same bound the host sizes the arenas
     // with: at most score / min(x, e) operations, each with a match run, item_chars characters per item); wfa_text_compact_kernel
     // moves it to its place in the dense arena
-    const uint32_t bound = (active && !fail) ? (uint32_t)p.item_chars * (2u * ((uint32_t)p.score[pair] / (uint32_t)p.min_op_cost) + 1u) + 1u : 0u;
+    const uint32_t bound = (active && !fail) ? (uint32_t)p.item_chars * (2u * ((uint32_t)p.score[pair] / (uint32_t)p.min_op_cost) + 1u + (uint32_t)p.extra_items) + 1u : 0u;
     const unsigned long long s_off = wave_alloc(p.scratch_top, bound, lane);
     if (active && !fail && s_off + bound > p.text_scratch_cap) fail = true;
     if (active) {
       uint32_t len = 0xFFFFFFFFu;
       int cost = 0;
       if (!fail) {
-        len = replay_any<OPS_LDS>(p.raw, OPS_LDS ? q_lds : q, nops, pv, tv, plen, tlen, p.text_scratch + s_off, p.x, p.oe - p.e, p.e, &cost, bound, true);
+        len = replay_any<OPS_LDS>(p.raw, OPS_LDS ? q_lds : q, nops, pv, tv, plen, tlen, ends, p.text_scratch + s_off, p.x, p.oe - p.e, p.e, &cost, bound, true);
         if (len != 0xFFFFFFFFu && len + 1u > bound) len = 0xFFFFFFFFu;
       }
       // (cigar_off: the text's place in the scratch until the compaction)
@@ -654,7 +691,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_kernel(const WfaTraceP
   }
   uint32_t len = 0;
   if (active && !fail) {
-    len = replay_any(p.raw, q, nops, pv, tv, plen, tlen, (char*)nullptr, 0, 0, 0, (int*)nullptr);
+    len = replay_any(p.raw, q, nops, pv, tv, plen, tlen, ends, (char*)nullptr, 0, 0, 0, (int*)nullptr);
     if (len == 0xFFFFFFFFu) fail = true;
   }
   const uint32_t need_txt = (active && !fail) ? len + 1u : 0u;
@@ -663,7 +700,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_kernel(const WfaTraceP
   if (active) {
     if (!fail) {
       int cost = 0;
-      replay_any(p.raw, q, nops, pv, tv, plen, tlen, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
+      replay_any(p.raw, q, nops, pv, tv, plen, tlen, ends, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
       finish_pair(p, pair, false, txt_off, len, cost, p.score[pair]);
     } else finish_pair(p, pair, true);
   }
@@ -778,9 +815,11 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_wave_kernel(const Wfa
     if (p.walk_only && need_ops > p.ops_slot) fail = true;
     uint8_t* const q_end = q_begin + need_ops;
     uint8_t* q = q_end;
+    const WalkSpan span = walk_span(p, pair, plen, tlen);
+    PairEnds ends{0, span.k1};
     if (!fail) {
       const BtBlock bb = bt_block(p, pair);
-      int k = tlen - plen, s = score, state = 0;       // state 0: M, 1: I, 2: D
+      int k = span.k1, s = score, state = 0;       // state 0: M, 1: I, 2: D
       int s_top = -1, kbase = 0;
       const int tile_w = bb.tiled ? 32 : 16;
       while (s > 0) {
@@ -798,7 +837,9 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_wave_kernel(const Wfa
         --q;
         if (lane == 0) *q = (uint8_t)op;
       }
-      if (!walk_ended(s, state, k)) fail = true;
+      if (!walk_ended(s, state, k, span)) fail = true;
+      ends.k0 = k;
+      if (!fail && p.ends && lane == 0) p.ends[2 * (size_t)pair] = k;
     }
     // the op list is read back by this same wavefront: make lane 0's stores visible to all lanes
     __threadfence_block();
@@ -823,7 +864,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_wave_kernel(const Wfa
     uint32_t len = 0;
     int cost = 0;
     if (!fail) {
-      len = replay<RAW>(q, nops, Pw, Tw, plen, tlen, lane == 0 ? text_lds : nullptr, p.x, p.oe - p.e, p.e, &cost, (uint32_t)p.text_lds_bytes);
+      len = replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, lane == 0 ? text_lds : nullptr, p.x, p.oe - p.e, p.e, &cost, (uint32_t)p.text_lds_bytes);
       if (len == 0xFFFFFFFFu) fail = true;
     }
     unsigned long long txt_off = 0;
@@ -838,7 +879,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_wave_kernel(const Wfa
         char* dst = p.text + txt_off;
         for (uint32_t i = lane; i <= len; i += 64) dst[i] = text_lds[i];
       } else {
-        replay<RAW>(q, nops, Pw, Tw, plen, tlen, lane == 0 ? p.text + txt_off : nullptr, p.x, p.oe - p.e, p.e, &cost);
+        replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, lane == 0 ? p.text + txt_off : nullptr, p.x, p.oe - p.e, p.e, &cost);
       }
       if (lane == 0) {
         p.cigar_off[pair] = txt_off;
@@ -900,9 +941,12 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_group_kernel(const Wf
     }
     uint8_t* const q_end = q_begin + need_ops;
     uint8_t* q = q_end;
+    WalkSpan span{0, 0, 0};
+    if (active) span = walk_span(p, pair, plen, tlen);
+    PairEnds ends{0, span.k1};
     if (active && !fail) {
       const BtBlock bb = bt_block(p, pair);
-      int k = tlen - plen, s = score, state = 0;       // state 0: M, 1: I, 2: D
+      int k = span.k1, s = score, state = 0;       // state 0: M, 1: I, 2: D
       int s_top = -1, kbase = 0;
       const int tile_w = bb.tiled ? 32 : 16;
       while (s > 0) {
@@ -919,7 +963,9 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_group_kernel(const Wf
         --q;
         if (sub == 0) *q = (uint8_t)op;
       }
-      if (!walk_ended(s, state, k)) fail = true;
+      if (!walk_ended(s, state, k, span)) fail = true;
+      ends.k0 = k;
+      if (!fail && p.ends && sub == 0) p.ends[2 * (size_t)pair] = k;
     }
     __threadfence_block();
     __builtin_amdgcn_wave_barrier();
@@ -928,7 +974,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_group_kernel(const Wf
     uint32_t len = 0;
     int cost = 0;
     if (active && !fail && sub == 0) {
-      len = replay<RAW>(q, nops, Pw, Tw, plen, tlen, text_lds, p.x, p.oe - p.e, p.e, &cost, (uint32_t)p.text_lds_bytes);
+      len = replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, text_lds, p.x, p.oe - p.e, p.e, &cost, (uint32_t)p.text_lds_bytes);
     }
     len = __shfl(len, lead);
     if (active && !fail && len == 0xFFFFFFFFu) fail = true;
@@ -942,7 +988,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_group_kernel(const Wf
         char* dst = p.text + txt_off;
         for (uint32_t i = sub; i <= len; i += L) dst[i] = text_lds[i];
       } else if (sub == 0) {
-        replay<RAW>(q, nops, Pw, Tw, plen, tlen, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
+        replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
       }
     }
     if (active && sub == 0) finish_pair(p, pair, fail, txt_off, len, cost, score);

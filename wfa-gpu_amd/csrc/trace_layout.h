@@ -66,6 +66,7 @@ struct TracePlanIn {
   long long s_hi;            // no pair of the chain finished above this score
   int min_op_cost;           // min(x, e)
   int item_chars;            // widest RLE item
+  int extra_items = 0;       // RLE items beyond 2 * operations + 1 (ends-free: the two free runs)
 };
 struct TracePlan {
   // the mapping fields of WfaTraceParams
@@ -103,7 +104,7 @@ inline TracePlan trace_plan_begin(const TracePlanIn& in) {
   // unbounded tier has no bound: those read the sums k_trace_bounds has formed.
   const unsigned long long s_pos = (unsigned long long)(in.s_hi > 0 ? in.s_hi : 0);
   tp.ops_bound = (unsigned long long)in.n_chain * ((s_pos + 3ull) & ~3ull);
-  tp.text_bound = (unsigned long long)in.n_chain * ((unsigned long long)in.item_chars * (2ull * (s_pos / (unsigned long long)in.min_op_cost) + 1ull) + 1ull);
+  tp.text_bound = (unsigned long long)in.n_chain * ((unsigned long long)in.item_chars * (2ull * (s_pos / (unsigned long long)in.min_op_cost) + 1ull + (unsigned long long)in.extra_items) + 1ull);
   // (the bound is sized by the chain's largest budget -- the caller's max_error once a re-run link follows -- for EVERY pair:
   // fine for the batches of a pipelined call, whose round trips it saves (62 500 x 1 kbp pairs: 225 MB), too generous for a
   // big resident batch (1M pairs at max_error 300: 3.6 GB of fresh device memory per buffer to save one counter read)

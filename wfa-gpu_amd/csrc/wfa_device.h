@@ -126,6 +126,10 @@ struct WfaAlignParams {
   // diagnostics (tuning.timed_barriers): barrier arrival / release clocks of workgroup 0, 3 x u64 per score and wave
   unsigned long long* dbg_times;
   uint32_t dbg_cap;              // records (scores) the buffer holds
+  // ends-free alignment (only the ENDSFREE instantiations, align_kernel_ef.hip, read these): the span as the caller gave it -- the
+  // kernel clamps each value to the pair's own sequence length -- and where the diagonal the alignment ended on goes
+  int span_pbf, span_pef, span_tbf, span_tef;   // pattern begin / pattern end / text begin / text end free
+  int32_t* ends;                 // [2 * pair + 1] out: end diagonal k1 ([2 * pair], the start diagonal k0, is the backtrace's; INT_MIN here)
 };
 
 struct WfaTraceParams {
@@ -169,6 +173,13 @@ struct WfaTraceParams {
   int item_chars;                // widest RLE item (digits of the longest sequence + 1): sizes the upper-bound text slots
   unsigned long long* cigar_off; // [pair] out: byte offset of the CIGAR in `text` (between walk and replay: of the op list in `ops`)
   uint32_t* cigar_len;           // [pair] out: strlen; 0xFFFFFFFF if it did not fit
+  // ends-free alignment.  ends == nullptr (and a span of zeros): end to end -- every walk starts on diagonal tlen - plen and ends on 0.
+  // Else ends[2 * pair + 1] is the diagonal k1 the walk starts on (written by the wavefront kernel), the walk may end on any diagonal
+  // k0 of [-min(span_pbf, plen), min(span_tbf, tlen)] and leaves it in ends[2 * pair]; the replay starts at (max(-k0, 0), max(k0, 0)),
+  // prints the free bases in front of and behind the path as D / I runs and prices the text without them.
+  int span_pbf, span_tbf;
+  int32_t* ends;
+  int extra_items;               // RLE items a text may have beyond 2 * operations + 1 (the two free runs): sizes the upper-bound text slots
 };
 
 // Host-side launchers (one per translation unit).
@@ -194,6 +205,17 @@ size_t wfa_align_lds_bytes(const WfaAlignParams& p, int tier);
 void wfa_launch_align(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream, int wpe = 8,
                       hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 int wfa_align_max_blocks_per_cu(int tier, bool with_bt, bool raw, bool banded, size_t lds_bytes, int wpe = 8);
+// The ends-free instantiations of the wavefront kernel (align_kernel_ef.hip: a translation unit and code object of their own, loaded
+// only by calls under a span): tiers 0, 1, 2 and 3, exact search, careful loop; same LDS footprint as the end-to-end ones.
+void wfa_launch_align_ef(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream,
+                         hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+int wfa_align_ef_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds_bytes);
+void wfa_prime_align_ef(hipStream_t stream);
+// The span of wfagpu_amd_configure_span (wfa_launch.hip): false when none is configured; out (optional) receives
+// {pattern begin, pattern end, text begin, text end} free.  wfa_lane_span: the span the calling thread -- a lane of
+// launch_alignments* -- wants its wfagpu_amd_align_device call to run under (nullptr: end to end), as four ints.
+bool wfa_configured_span(int* out4);
+const int* wfa_lane_span4();
 bool wfa_launch_trace(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);     // false: nothing to launch
 // Tier 5 (short_kernel.hip): 64 / lanes alignments per wavefront (lanes = 16 or 32 diagonals each), rings in registers; with_bt: one row
 // of `lanes` origin bytes per score for the backtrace.

@@ -375,6 +375,7 @@ struct wfagpu_amd_ctx {
   // kernels of batch j+1 run (launch_alignments*: the copy left the lanes' critical path).
   DevBuf text[2], cig_off[2], cig_len[2];
   DevBuf dbg;               // tuning.timed_barriers: barrier records of workgroup 0
+  DevBuf ends;              // ends-free calls whose caller does not ask for the diagonals: the backtrace needs them all the same
   int dbg_waves = 0; unsigned dbg_records = 0;
   int out_set = 0;
   unsigned long long* h_counters = nullptr;  // pinned
@@ -448,7 +449,7 @@ void wfagpu_amd_destroy(wfagpu_amd_ctx_t* c) {
   hipStreamSynchronize(c->stream);      // (nullptr: the null stream)
   c->free_retired();
   for (DevBuf* b : {&c->packed, &c->flags, &c->status, &c->cells, &c->bt_final, &c->list_a, &c->list_b, &c->list_c, &c->list_d, &c->list_e, &c->work_ctr, &c->sample, &c->ratio, &c->budget,
-                    &c->counters, &c->arena, &c->ops, &c->text[0], &c->text[1], &c->text_scratch, &c->cig_off[0], &c->cig_off[1], &c->cig_len[0], &c->cig_len[1], &c->gring, &c->dbg})
+                    &c->counters, &c->arena, &c->ops, &c->text[0], &c->text[1], &c->text_scratch, &c->cig_off[0], &c->cig_off[1], &c->cig_len[0], &c->cig_len[1], &c->gring, &c->dbg, &c->ends})
     b->release();
   if (c->h_counters) hipHostFree(c->h_counters);
   for (hipEvent_t ev : {c->ev_start, c->ev_pack, c->ev_a0, c->ev_a1, c->ev_b0, c->ev_b1, c->ev_t0, c->ev_t1, c->ev_end})
@@ -501,6 +502,7 @@ int wfagpu_amd_prime(wfagpu_amd_ctx_t* c) {
   wfa_prime_trace(c->stream);
   wfa_prime_pack(c->stream);
   wfa_prime_short(c->stream);
+  if (wfa_configured_span(nullptr)) wfa_prime_align_ef(c->stream);      // (the ends-free kernels: only callers under a span load them)
   LAUNCH_K(k_iota, dim3(1), dim3(64), 0, c->stream, static_cast<uint32_t*>(nullptr), 0u, 0u);      // (this file's)
   HIP_TRY(hipGetLastError());
   c->primed = true;
@@ -576,11 +578,20 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     *out = {best_t, p.band_width, max_score, best_lds, best_nb};
     return true;
   }
-  const int width = window_width(max_score, p.oe - p.e, p.e, max_seq_len);
+  // Ends-free (p.ends): the window is the end-to-end one around the hull of the start and end diagonals -- wider by at most the
+  // free bases (clamped to the sequences).  A bound for the longest pair, not an exact figure: a pair whose own window is wider
+  // comes back as a BAND failure and is escalated like any other.  Tiers 0, 1, 2 and 3 only.
+  const bool ef = p.ends != nullptr;
+  int width = window_width(max_score, p.oe - p.e, p.e, max_seq_len);
+  if (ef) {
+    const long long m = max_seq_len;
+    const long long free_sum = std::min<long long>(p.span_pbf, m) + std::min<long long>(p.span_pef, m) + std::min<long long>(p.span_tbf, m) + std::min<long long>(p.span_tef, m);
+    width = (int)std::min<long long>(2ll * max_seq_len + 1, (long long)width + free_sum);
+  }
   // Short wavefronts, score only (tier 5, short_kernel.hip): when the diagonal window of the budget fits 16 or 32 lanes, four or two
   // alignments share a wavefront and the rings live in registers (BASELINE configs[1]: 150 bp reads, budgets of ~14 once
   // they are tuned).  Pairs whose own window is wider (large |tlen - plen|) come back as BAND failures and go on as always.
-  if (!raw && !(p.ascii && !c->short_ascii_ok) && c->tuning.min_tier == 0 && !(bt && c->tuning.no_short_cigar) && wfa_short_supported(p.x, p.oe, p.e) && width + 1 <= 32 && max_score <= 30000) {
+  if (!ef && !raw && !(p.ascii && !c->short_ascii_ok) && c->tuning.min_tier == 0 && !(bt && c->tuning.no_short_cigar) && wfa_short_supported(p.x, p.oe, p.e) && width + 1 <= 32 && max_score <= 30000) {
     const int lanes = width + 1 <= 16 ? 16 : 32;
     p.rs = 0;
     const size_t lds = wfa_short_lds_bytes(p, lanes, bt);
@@ -608,13 +619,13 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     if (t == 0 && (width > 1024 || p.dm > 64)) continue;
     if (t == 1 && width > 8192) continue;
     if (t == 1 && few_pairs && width >= 1024 && !min_tier && wfa_align_lds_bytes(p, 2) <= budget[2]) continue;
-    int nb = wfa_align_max_blocks_per_cu(t, bt, raw, false, lds);
+    int nb = ef ? wfa_align_ef_max_blocks_per_cu(t, bt, raw, lds) : wfa_align_max_blocks_per_cu(t, bt, raw, false, lds);
     if (nb < 1) continue;
     // Occupancy-matched instantiation of the one-wave kernels: LDS decides how many rings a CU holds; compiled for 8 waves
     // per SIMD the kernel lives on 64 VGPRs and 78 SGPRs (123 scalar spills + scratch), which only pays when 8 waves per
     // SIMD really are resident.  The smallest of 4 / 6 / 7 / 8 that keeps all the rings LDS allows but at most one.
     int wpe = 8;
-    if (t == 0 && !raw) {
+    if (t == 0 && !raw && !ef) {
       const int forced = c->tuning.waves_per_simd;
       for (int w : {4, 6, 7, 8}) if (4 * w >= nb - 1) { wpe = w; break; }
       // (gap extensions > 1: the general lean loop carries more scalar state than the e == 1 loop; compiled for 8 waves per SIMD -- 64
@@ -632,7 +643,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     // (profiles/r02/mid_lengths.txt).  tuning.t0_min_blocks: A/B.
     const int t0_min_blocks = c->tuning.t0_min_blocks > 0 ? c->tuning.t0_min_blocks : 10;
     if (t == 0 && !min_tier && nb < t0_min_blocks && width >= 384) continue;
-    if (t == 1 && !raw && c->tuning.exact_two_waves) {
+    if (t == 1 && !raw && !ef && c->tuning.exact_two_waves) {
       // A/B hook: TWO waves per alignment where four would run (same ring, same LDS; half the per-score bookkeeping per chunk, half the waves)
       const size_t lds2 = wfa_align_lds_bytes(p, 6);
       const int nb2 = wfa_align_max_blocks_per_cu(6, bt, raw, false, lds2);
@@ -642,7 +653,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     return true;
   }
   // hybrid ring: everything but the D rows in LDS (one workgroup of 16 waves per CU)
-  if (i16_ok && !raw && min_tier != 3) {
+  if (i16_ok && !raw && !ef && min_tier != 3) {
     const size_t lds_h = wfa_align_lds_bytes(p, 4);
     if (lds_h <= c->lds_per_block_max) {
       const int nb = wfa_align_max_blocks_per_cu(4, bt, raw, false, lds_h);
@@ -652,7 +663,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   p.rs = rs_plain;
   const size_t lds = wfa_align_lds_bytes(p, 3);
   if (lds > c->lds_per_block_max) return false;   // sequences themselves do not fit LDS
-  const int nb = wfa_align_max_blocks_per_cu(3, bt, raw, false, lds);
+  const int nb = ef ? wfa_align_ef_max_blocks_per_cu(3, bt, raw, lds) : wfa_align_max_blocks_per_cu(3, bt, raw, false, lds);
   *out = {3, width, max_score, lds, std::max(1, std::min(nb, 2))};
   return true;
 }
@@ -677,12 +688,20 @@ int zero_counter(wfagpu_amd_ctx* c, int idx, int count = 1) {
 
 }  // namespace
 
-extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
-                                       affine_penalties_t pen, int max_error, int band, int band_width,
-                                       bool compute_cigar, int32_t* d_scores,
-                                       const char** d_text, const unsigned long long** d_off,
-                                       const unsigned int** d_len) {
+// span == nullptr: end to end.  Else the ends-free kernels (align_kernel_ef.hip), exact search; d_ends: see the header.
+static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
+                             affine_penalties_t pen, int max_error, int band, int band_width,
+                             bool compute_cigar, int32_t* d_scores,
+                             const char** d_text, const unsigned long long** d_off,
+                             const unsigned int** d_len, const wfagpu_amd_span_t* span, int32_t* d_ends) {
   if (!c || !b || !d_scores) return -1;
+  const bool ef = span != nullptr;
+  if (ef) { band = -1; band_width = 0; }      // (exact search: a band is a permission to approximate, not an obligation)
+  if (ef && (span->pattern_begin_free < 0 || span->pattern_end_free < 0 || span->text_begin_free < 0 || span->text_end_free < 0)) {
+    fprintf(stderr, "[!] ERROR: the members of a span must not be negative (got %d,%d,%d,%d)\n", span->pattern_begin_free, span->pattern_end_free,
+            span->text_begin_free, span->text_end_free);
+    return -1;
+  }
   if (pen.x <= 0 || pen.o < 0 || pen.e <= 0) {
     fprintf(stderr, "[!] ERROR: penalties must be x>0, o>=0, e>0 (got %d,%d,%d)\n", pen.x, pen.o, pen.e);
     return -1;
@@ -744,7 +763,17 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
   for (unsigned v = batch_max_len; v >= 10; v /= 10) ++item_chars;
   item_chars = std::max(item_chars, 6);      // (the emit kernels' one-word fast path writes 4 bytes per item)
 
+  // ends-free: two RLE items more per text (the free runs), and the diagonals -- the backtrace needs them whoever asks
+  const int extra_items = ef ? 2 : 0;
+  if (ef && !d_ends) {
+    if (c->ends.ensure((size_t)8 * n, st)) return -1;
+    d_ends = static_cast<int32_t*>(c->ends.p);
+  }
   WfaAlignParams ap{};
+  if (ef) {
+    ap.span_pbf = span->pattern_begin_free; ap.span_pef = span->pattern_end_free; ap.span_tbf = span->text_begin_free; ap.span_tef = span->text_end_free;
+    ap.ends = d_ends;
+  }
   ap.packed = prepacked ? static_cast<const uint32_t*>(b->d_packed) : static_cast<const uint32_t*>(c->packed.p);
   ap.meta = reinterpret_cast<const WfaSeqPair*>(b->d_metadata);
   ap.x = pen.x; ap.oe = oe; ap.e = pen.e;
@@ -775,6 +804,12 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
     return 64.0 * (double)((w + 15) / 16) * (double)(B / 4 + 1) + 512.0;
   };
   est_pair_bytes = std::max(est_pair_bytes, tiled_pair_bytes(std::min<long long>(max_error, 2ll * batch_max_len * std::max(pen.x, pen.e))));
+  if (ef) {
+    // (ends-free: every score's row starts as wide as the free begins and only grows: rows behind a row table in every tier)
+    const double m = batch_max_len;
+    const double start_w = std::min<double>(span->pattern_begin_free, m) + std::min<double>(span->text_begin_free, m) + 1.0;
+    est_pair_bytes += start_w * (double)std::min<unsigned>(max_error, 2 * max_len);
+  }
   if (compute_cigar) {
     // arena: expected need, bounded by configuration / free memory / 32-bit unit addressing
     size_t want = c->arena_cfg;
@@ -808,7 +843,7 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
   // 18 us + the gap between two launches of a 168 us step of 100k configs[1] pairs.  (ASCII dword indices are 32-bit there.)
   // (sequences_bytes may be missing from a caller's batch record: four times the packed words bound the ASCII layout from above)
   c->short_ascii_ok = std::max<size_t>(b->sequences_bytes, b->packed_bytes * 4) < ((size_t)1 << 34);
-  const bool short_fuses = wfa_short_supported(pen.x, oe, pen.e) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
+  const bool short_fuses = !ef && wfa_short_supported(pen.x, oe, pen.e) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
   const bool fused_pack = !prepacked && (b->max_seq_len >= 512u || short_fuses) && !c->tuning.no_fused_pack;
   // Every status starts as PENDING = 0: written by the pack kernel where it runs (it visits every pair anyway), by a memset (a
   // launch of its own, ~5 us + a gap) where it does not -- queued by whoever reads the array first (ensure_status), and not at all
@@ -1062,6 +1097,7 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
           // (with CIGARs the launch owns n_cur slots above the bump pointer: move it past them for whatever allocates next)
           if (cigar_now && !ap.arena_top_known) LAUNCH_K(k_bump, dim3(1), dim3(64), 0, st, ap.arena_top, (unsigned long long)n_cur * wfa_short_bt_slot_units(ap.max_score, tp.wpe), ap.arena_units);
         }
+        else if (ef) wfa_launch_align_ef(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else wfa_launch_align(ap, tp.tier, cigar_now, raw, grid, st, tp.wpe, L.e0, L.e1);
         {
           const hipError_t le = hipGetLastError();
@@ -1122,7 +1158,7 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
                                static_cast<const uint32_t*>(c->cells.p), std::min(pen.x, pen.e), item_chars, ct, n);
       if (cigar_now) {
         // which kernels walk and replay (trace_layout.h: two steps, the largest score of the pass arrives with the counters)
-        const TracePlanIn plan_in{c->lds_per_block_max, c->tuning.trace_mode, c->tuning.emit_pairs, raw, max_len, n_chain, s_hi, std::min(pen.x, pen.e), item_chars};
+        const TracePlanIn plan_in{c->lds_per_block_max, c->tuning.trace_mode, c->tuning.emit_pairs, raw, max_len, n_chain, s_hi, std::min(pen.x, pen.e), item_chars, extra_items};
         TracePlan plan = trace_plan_begin(plan_in);
         unsigned long long ops_need, text_sum;
         if (plan.by_bound) { ops_need = plan.ops_bound + 256; text_sum = plan.text_bound; }
@@ -1134,6 +1170,7 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
           if (read_counters(c)) return -1;
           ops_need = c->h_counters[CT_SUM_OPS] + 256; text_sum = c->h_counters[CT_SUM_TEXT];
         }
+        if (!plan.by_bound) text_sum += (unsigned long long)n_chain * (unsigned long long)(item_chars * extra_items);      // (the device's sum knows nothing of the free runs)
         trace_plan_finish(plan, plan_in, c->h_counters[CT_MAX_SCORE]);
         const unsigned long long text_need = text_used + text_sum + 256;
         if (c->ops.ensure(ops_need, st)) return -1;
@@ -1159,6 +1196,8 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
         tp.text = static_cast<char*>(c->text[c->out_set].p); tp.text_cap = c->text[c->out_set].cap; tp.text_top = ct + CT_TEXT;
         tp.min_op_cost = std::min(pen.x, pen.e);
         tp.item_chars = item_chars;
+        tp.extra_items = extra_items;
+        if (ef) { tp.span_pbf = ap.span_pbf; tp.span_tbf = ap.span_tbf; tp.ends = d_ends; }
         if (plan.text_scratch) {
           if (c->text_scratch.ensure(text_sum + 4096, st)) return -1;
           if (zero_counter(c, CT_SCRATCH)) return -1;
@@ -1305,7 +1344,7 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
       // (tuned budgets pay where they narrow a wide window -- or, score-only, where they bring it down to what the
       // several-alignments-per-wavefront tier holds)
       const bool short_ok = wfa_short_supported(pen.x, oe, pen.e) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar);
-      const bool would_tune = n >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) && (w_me > 128 || (w_me > 15 && short_ok));
+      const bool would_tune = !ef && n >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) && (w_me > 128 || (w_me > 15 && short_ok));
       bool inherited = false;
       if (would_tune && c->same_stream)
         for (int i = 0; i < c->n_saved_q; ++i) {
@@ -1350,7 +1389,8 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
       const int w_me2 = window_width(max_error, pen.o, pen.e, max_len);
       const bool short_ok2 = wfa_short_supported(pen.x, oe, pen.e) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar);
       // (the budgets decide whether the band is worth using and serve the exact kernels; with the band forced neither applies)
-      const bool try_budget = !raw && n_pending >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) &&
+      // (ends-free: no budgets from a sample -- the careful loop is the only one, and a read's score says little about a window's)
+      const bool try_budget = !ef && !raw && n_pending >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) &&
                               (w_me2 > 128 || (w_me2 > 15 && short_ok2));
       int saved_idx = -1;
       if (try_budget && c->same_stream) {
@@ -1501,4 +1541,25 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
   }
   if (rc == 0 && (ct_clean || hipMemsetAsync(c->counters.p, 0, CT_BYTES + 8 * 64, st) == hipSuccess)) c->counters_zeroed = true;
   return rc;
+}
+
+extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
+                                       affine_penalties_t pen, int max_error, int band, int band_width,
+                                       bool compute_cigar, int32_t* d_scores,
+                                       const char** d_text, const unsigned long long** d_off,
+                                       const unsigned int** d_len) {
+  // (a lane of launch_alignments* under a configured span: wfa_launch.hip hands the span over in a thread-local, so that the seam
+  // needs nothing from this file that it did not need before)
+  const int* const ls = wfa_lane_span4();
+  if (ls) {
+    const wfagpu_amd_span_t span{ls[0], ls[1], ls[2], ls[3]};
+    return align_device_impl(c, b, pen, max_error, band, band_width, compute_cigar, d_scores, d_text, d_off, d_len, &span, nullptr);
+  }
+  return align_device_impl(c, b, pen, max_error, band, band_width, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr);
+}
+
+extern "C" int wfagpu_amd_align_device_span(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b, affine_penalties_t pen, int max_error,
+                                            const wfagpu_amd_span_t* span, bool compute_cigar, int32_t* d_scores, int32_t* d_ends,
+                                            const char** d_text, const unsigned long long** d_off, const unsigned int** d_len) {
+  return align_device_impl(c, b, pen, max_error, -1, 0, compute_cigar, d_scores, d_text, d_off, d_len, span, span ? d_ends : nullptr);
 }

@@ -42,6 +42,35 @@
 #include <sched.h>
 
 #include "../../include/wfa_gpu_device.h"
+
+// The process-wide span (wfagpu_amd_configure_span): what launch_alignments*, wfagpu_align and the CLI align under.  It lives here,
+// with the rest of the seam's configuration; the host driver is told per call, through a thread-local that a lane sets around its
+// wfagpu_amd_align_device call (wfa_lane_span4), so that this file calls nothing of the driver that it did not call before.
+namespace {
+std::mutex g_span_mutex;
+bool g_span_set = false;
+int g_span[4] = {0, 0, 0, 0};
+thread_local const int* t_lane_span = nullptr;
+}  // namespace
+
+bool wfa_configured_span(int* out4) {
+  std::lock_guard<std::mutex> lock(g_span_mutex);
+  if (out4 && g_span_set) for (int i = 0; i < 4; ++i) out4[i] = g_span[i];
+  return g_span_set;
+}
+const int* wfa_lane_span4() { return t_lane_span; }
+
+extern "C" int wfagpu_amd_configure_span(const wfagpu_amd_span_t* span) {
+  if (span && (span->pattern_begin_free < 0 || span->pattern_end_free < 0 || span->text_begin_free < 0 || span->text_end_free < 0)) {
+    fprintf(stderr, "[!] ERROR: the members of a span must not be negative (got %d,%d,%d,%d)\n", span->pattern_begin_free, span->pattern_end_free,
+            span->text_begin_free, span->text_end_free);
+    return -1;
+  }
+  std::lock_guard<std::mutex> lock(g_span_mutex);
+  g_span_set = span != nullptr;
+  if (span) { g_span[0] = span->pattern_begin_free; g_span[1] = span->pattern_end_free; g_span[2] = span->text_begin_free; g_span[3] = span->text_end_free; }
+  return 0;
+}
 #include "../utils/logger.h"
 #include "../utils/verification.h"
 
@@ -166,6 +195,10 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
   std::atomic<long> correct{0}, incorrect{0};
   std::atomic<long long> sum{0};
   std::atomic<long> next{(long)from};
+  // (under a configured span the alignments are ends-free: the text is priced without its free runs, the score checked against
+  // the program with free borders -- utils/verification.h)
+  int sp4[4] = {0, 0, 0, 0};
+  const int* const span = wfa_configured_span(sp4) ? sp4 : nullptr;
   auto worker = [&](unsigned) {
     verification_scratch_t scratch = {nullptr, 0};     // this worker's, for all its pairs; freed below
     for (;;) {
@@ -181,13 +214,17 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
         if (a.cigar) {
           const char* cg = a.results[i].cigar.buffer;
           const bool c1 = check_cigar_edit(text, pattern, m.text_len, m.pattern_len, cg);
-          const bool c2 = check_affine_distance(text, pattern, m.text_len, m.pattern_len, dist, a.opt.penalties.x,
-                                                a.opt.penalties.o, a.opt.penalties.e, cg);
+          const bool c2 = span ? check_affine_distance_span(text, pattern, m.text_len, m.pattern_len, dist, a.opt.penalties.x,
+                                                            a.opt.penalties.o, a.opt.penalties.e, cg, span)
+                               : check_affine_distance(text, pattern, m.text_len, m.pattern_len, dist, a.opt.penalties.x,
+                                                       a.opt.penalties.o, a.opt.penalties.e, cg);
           if (!c1) LOG_ERROR("Incorrect cigar (%ld). Distance: %d. CIGAR: %s", i, dist, cg);
           ok = c1 && c2;
         }
-        const int cpu = verification_cpu_score_scratch(pattern, text, m.pattern_len, m.text_len, a.opt.penalties.x,
-                                                       a.opt.penalties.o, a.opt.penalties.e, &scratch);
+        const int cpu = span ? verification_cpu_score_span_scratch(pattern, text, m.pattern_len, m.text_len, a.opt.penalties.x,
+                                                                   a.opt.penalties.o, a.opt.penalties.e, span, &scratch)
+                             : verification_cpu_score_scratch(pattern, text, m.pattern_len, m.text_len, a.opt.penalties.x,
+                                                              a.opt.penalties.o, a.opt.penalties.e, &scratch);
         if (cpu != dist) { LOG_ERROR("Incorrect distance (%ld). GPU=%d, CPU=%d", i, dist, cpu); ok = false; }
         sum += dist;
         if (ok) ++correct; else ++incorrect;
@@ -869,8 +906,18 @@ int run_device(const CallArgs& a, Shard& sh) {
       // the budgets a lane learnt from a sample stay on trial (same penalties, same max_error, same length bucket; results are
       // exact either way, and a batch in which more than 5 % of the pairs miss them makes the next one sample again).
       wfagpu_amd_hint_same_stream(L.ctx, 1);
+      // (under a configured span -- wfagpu_amd_configure_span -- every batch of every lane and device slot runs ends-free, exactly: a
+      // band that the options ask for is not used, said once)
+      int sp4[4];
+      const bool under_span = wfa_configured_span(sp4);
+      if (under_span && a.opt.band > 0 && a.opt.threads_per_block > 0) {
+        static std::atomic<bool> warned{false};
+        if (!warned.exchange(true)) fprintf(stderr, "[!] WARNING: the adaptive band is not combined with an ends-free span: running the exact search\n");
+      }
+      t_lane_span = under_span ? sp4 : nullptr;
       const int arc = wfagpu_amd_align_device(L.ctx, &wb, a.opt.penalties, a.opt.max_error, a.opt.band, a.opt.threads_per_block, a.cigar,
                                               d_sc, &bo.d_text, &bo.d_off, &bo.d_len);
+      t_lane_span = nullptr;
       if (arc) return arc;
       bo.d_scores = d_sc;
       if (a.cigar) { wfagpu_amd_stats_t stt; wfagpu_amd_last_stats(L.ctx, &stt); bo.text_bytes = stt.text_bytes; }

@@ -57,6 +57,8 @@ static void usage(const char* prog) {
            "\t-b, --batch-size <int>            Alignments per batch (default: all)\n"
            "\t-B, --band <int|auto>             Adaptive band: re-centring period (auto = 25)\n"
            "\t-c, --check                       Verify results against a CPU computation\n"
+           "\t    --ends-free <pb,pe,tb,te>     Ends-free alignment: bases that may stay unaligned at no cost at the pattern's\n"
+           "\t                                  begin / end and the text's begin / end (exact search: not with -B)\n"
            "[System]\n"
            "\t-t, --threads-per-block <int>     Accepted for compatibility (band width in banded mode)\n"
            "\t-w, --workers <int>               Accepted for compatibility\n"
@@ -78,10 +80,12 @@ int main(int argc, char** argv) {
         {"compute-cigar", no_argument, 0, 'x'}, {"max-distance", required_argument, 0, 'e'},
         {"batch-size", required_argument, 0, 'b'}, {"band", required_argument, 0, 'B'},
         {"check", no_argument, 0, 'c'}, {"threads-per-block", required_argument, 0, 't'},
-        {"workers", required_argument, 0, 'w'}, {"help", no_argument, 0, 'h'}, {"stage-times", no_argument, 0, 1000}, {0, 0, 0, 0}};
+        {"workers", required_argument, 0, 'w'}, {"help", no_argument, 0, 'h'}, {"stage-times", no_argument, 0, 1000},
+        {"ends-free", required_argument, 0, 1001}, {0, 0, 0, 0}};
     const char *seq_path = NULL, *q_path = NULL, *t_path = NULL, *out_path = NULL, *pen_str = NULL;
     long n_read = 0, max_distance = -1, batch_size = -1, band_arg = -2, tpb = -1, workers = -1;
     bool print_out = false, verbose = false, cigar = false, check = false, stage_times = false;
+    const char* span_str = NULL;
 
 
     int c;
@@ -104,6 +108,7 @@ int main(int argc, char** argv) {
             case 't': tpb = atol(optarg); break;
             case 'w': workers = atol(optarg); break;
             case 1000: stage_times = true; break;      /* (not in the reference: the library's stage clocks of the call on stderr) */
+            case 1001: span_str = optarg; break;       /* (not in the reference: WFA2's ends-free alignment) */
             case 'h': usage(argv[0]); exit(0);
             default: break;      /* an option the tool does not know is skipped, like the reference's parser does (utils/arg_handler.c:97-140) */
         }
@@ -114,6 +119,26 @@ int main(int argc, char** argv) {
         return 1;
     }
 
+    /* --ends-free: four non-negative integers, nothing behind them; not together with the adaptive band.  Checked before any
+     * device work: the device query thread starts below. */
+    if (span_str) {
+        wfagpu_amd_span_t span;
+        char tail = 0;
+        if (sscanf(span_str, "%d,%d,%d,%d%c", &span.pattern_begin_free, &span.pattern_end_free, &span.text_begin_free, &span.text_end_free, &tail) != 4 ||
+            span.pattern_begin_free < 0 || span.pattern_end_free < 0 || span.text_begin_free < 0 || span.text_end_free < 0) {
+            LOG_ERROR("--ends-free takes four non-negative integers pb,pe,tb,te (got \"%s\").", span_str)
+            usage(argv[0]);
+            return 1;
+        }
+        if (band_arg != -2) {
+            LOG_ERROR("--ends-free is an exact search: it is not combined with the adaptive band (-B).")
+            usage(argv[0]);
+            return 1;
+        }
+        if (wfagpu_amd_configure_span(&span) != 0) return 1;
+        LOG_INFO("Ends-free alignment: pattern begin/end free %d/%d, text begin/end free %d/%d.", span.pattern_begin_free, span.pattern_end_free,
+                 span.text_begin_free, span.text_end_free)
+    }
     int x = 2, o = 3, e = 1;
     if (pen_str && sscanf(pen_str, "%d,%d,%d", &x, &o, &e) != 3) {
         LOG_WARN("Invalid penalties format provided. Using default penalties (0,2,3,1).")

@@ -140,3 +140,123 @@ int verification_cpu_score_scratch(const char* pattern, const char* text, size_t
     }
     return s;
 }
+
+/* ---- ends-free (see verification.h) ---- */
+static void clamp_span(const int* span, int plen, int tlen, int* pb, int* pe, int* tb, int* te) {
+    *pb = *pe = *tb = *te = 0;
+    if (!span) return;
+    *pb = span[0] < plen ? span[0] : plen; *pe = span[1] < plen ? span[1] : plen;
+    *tb = span[2] < tlen ? span[2] : tlen; *te = span[3] < tlen ? span[3] : tlen;
+    if (*pb < 0) *pb = 0;
+    if (*pe < 0) *pe = 0;
+    if (*tb < 0) *tb = 0;
+    if (*te < 0) *te = 0;
+}
+
+bool check_affine_distance_span(const char* text, const char* pattern, size_t tlen, size_t plen,
+                                int distance, int x, int o, int e, const char* cigar, const int* span) {
+    (void)text; (void)pattern;
+    int pb, pe, tb, te;
+    clamp_span(span, (int)plen, (int)tlen, &pb, &pe, &tb, &te);
+    /* items first: the last one is only known at the end */
+    size_t n_items = 0;
+    for (const char* c = cigar; *c;) { long n; char op; c = next_item(c, &n, &op); if (!c) return false; ++n_items; }
+    long cost = 0;
+    char prev = 0;
+    size_t idx = 0;
+    const char* c = cigar;
+    while (*c) {
+        long n = 0; char op = 0;
+        c = next_item(c, &n, &op);      /* (well-formed: checked above) */
+        if (op == 'I' || op == 'D') {
+            long paid = n;
+            if (idx == 0) { const long f = op == 'I' ? tb : pb; paid -= f < paid ? f : paid; }
+            if (idx + 1 == n_items) { const long f = op == 'I' ? te : pe; paid -= f < paid ? f : paid; }
+            if (paid > 0) cost += (prev == op ? 0 : o) + paid * e;
+        } else if (op == 'X') cost += n * x;
+        else if (op != 'M') return false;
+        prev = op;
+        ++idx;
+    }
+    return cost == distance;
+}
+
+int verification_cpu_score_span(const char* pattern, const char* text, size_t plen, size_t tlen, int x, int o, int e, const int* span) {
+    verification_scratch_t sc = {NULL, 0};
+    const int s = verification_cpu_score_span_scratch(pattern, text, plen, tlen, x, o, e, span, &sc);
+    verification_scratch_free(&sc);
+    return s;
+}
+
+/* The program of verification_cpu_score_scratch with free borders: score 0 holds every diagonal of [-pbf, tbf] at offset
+ * max(k, 0); the alignment ends with the first score one of whose M cells has used up the text with at most pef pattern
+ * bases left, or the pattern with at most tef text bases left. */
+int verification_cpu_score_span_scratch(const char* pattern, const char* text, size_t plen_, size_t tlen_,
+                                        int x, int o, int e, const int* span, verification_scratch_t* sc) {
+    const int plen = (int)plen_, tlen = (int)tlen_;
+    int pbf, pef, tbf, tef;
+    clamp_span(span, plen, tlen, &pbf, &pef, &tbf, &tef);
+    const int W = plen + tlen + 5, K0 = plen + 2;
+    const int NONE = -(1 << 28);
+    const int oe = o + e;
+    const int depth = (x > oe ? x : oe) + 1;
+    const size_t need = (size_t)W * 3 * (size_t)depth;
+    if (!sc) return -1;
+    if (need > sc->cap) {
+        free(sc->buf);
+        sc->cap = need + need / 4;
+        sc->buf = (int*)malloc(sizeof(int) * sc->cap);
+        if (!sc->buf) { sc->cap = 0; return -1; }
+    }
+    int* M = sc->buf; int* I = M + (size_t)W * depth; int* D = I + (size_t)W * depth;
+    int lo = -pbf, hi = tbf;     /* diagonal span that can be non-empty at the current score */
+    /* the span of score 0 and its guards, in every slot */
+    for (int r = 0; r < depth; ++r)
+        for (int k = lo - 1; k <= hi + 1; ++k) { M[(size_t)r * W + K0 + k] = NONE; I[(size_t)r * W + K0 + k] = NONE; D[(size_t)r * W + K0 + k] = NONE; }
+    for (int k = lo; k <= hi; ++k) {
+        int h = k > 0 ? k : 0, v = h - k;
+        while (v < plen && h < tlen && pattern[v] == text[h]) { ++v; ++h; }
+        M[K0 + k] = h;
+        if ((h >= tlen && plen - v <= pef) || (v >= plen && tlen - h <= tef)) return 0;
+    }
+    int s;
+    for (s = 1;; ++s) {
+        int* Ms = M + (size_t)(s % depth) * W; int* Is = I + (size_t)(s % depth) * W; int* Ds = D + (size_t)(s % depth) * W;
+        const int* Mx = s >= x ? M + (size_t)((s - x) % depth) * W : NULL;
+        const int* Mo = s >= oe ? M + (size_t)((s - oe) % depth) * W : NULL;
+        const int* Ie = s >= e ? I + (size_t)((s - e) % depth) * W : NULL;
+        const int* De = s >= e ? D + (size_t)((s - e) % depth) * W : NULL;
+        if (lo > -plen) {
+            --lo;
+            for (int r = 0; r < depth; ++r) { M[(size_t)r * W + K0 + lo - 1] = NONE; I[(size_t)r * W + K0 + lo - 1] = NONE; D[(size_t)r * W + K0 + lo - 1] = NONE; }
+        }
+        if (hi < tlen) {
+            ++hi;
+            for (int r = 0; r < depth; ++r) { M[(size_t)r * W + K0 + hi + 1] = NONE; I[(size_t)r * W + K0 + hi + 1] = NONE; D[(size_t)r * W + K0 + hi + 1] = NONE; }
+        }
+        bool ended = false;
+        for (int k = lo; k <= hi; ++k) {
+            int ins = NONE, del = NONE, mis = NONE;
+            if (Mo && Mo[K0 + k - 1] > ins) ins = Mo[K0 + k - 1];
+            if (Ie && Ie[K0 + k - 1] > ins) ins = Ie[K0 + k - 1];
+            if (ins >= 0) ++ins;
+            if (Mo && Mo[K0 + k + 1] > del) del = Mo[K0 + k + 1];
+            if (De && De[K0 + k + 1] > del) del = De[K0 + k + 1];
+            if (Mx && Mx[K0 + k] >= 0) mis = Mx[K0 + k] + 1;
+            if (ins >= 0 && (ins > tlen || ins - k > plen)) ins = NONE;
+            if (del >= 0 && (del > tlen || del - k > plen)) del = NONE;
+            if (mis >= 0 && (mis > tlen || mis - k > plen)) mis = NONE;
+            Is[K0 + k] = ins; Ds[K0 + k] = del;
+            int m = mis > ins ? mis : ins; if (del > m) m = del;
+            if (m >= 0) {
+                int h = m, v = m - k;
+                while (v < plen && h < tlen && pattern[v] == text[h]) { ++v; ++h; }
+                m = h;
+                if ((h >= tlen && plen - v <= pef) || (v >= plen && tlen - h <= tef)) ended = true;
+            }
+            Ms[K0 + k] = m;
+        }
+        if (ended) break;
+    }
+    return s;
+}

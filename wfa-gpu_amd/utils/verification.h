@@ -35,6 +35,20 @@ void verification_scratch_free(verification_scratch_t* scratch);
 int verification_cpu_score(const char* pattern, const char* text, size_t plen, size_t tlen,
                            int x, int o, int e);
 
+/* Ends-free alignment (wfagpu_amd_span_t; include/wfa_gpu_device.h).  span = {pattern_begin_free, pattern_end_free,
+ * text_begin_free, text_end_free}, each clamped to its sequence here; NULL: end to end.
+ * The CIGAR of an ends-free alignment covers both whole sequences (check_cigar_edit as it is); its cost is taken
+ * WITHOUT the free bases: a leading D (I) run is free for as many bases as pattern_begin_free (text_begin_free)
+ * allows, a trailing one for pattern_end_free (text_end_free).  The score itself is checked against the dynamic
+ * program below, which starts on the free part of the first row / column and stops at the first score whose
+ * wavefront reaches the free part of the last ones. */
+bool check_affine_distance_span(const char* text, const char* pattern, size_t tlen, size_t plen,
+                                int distance, int x, int o, int e, const char* cigar, const int* span);
+int verification_cpu_score_span_scratch(const char* pattern, const char* text, size_t plen, size_t tlen,
+                                        int x, int o, int e, const int* span, verification_scratch_t* scratch);
+int verification_cpu_score_span(const char* pattern, const char* text, size_t plen, size_t tlen,
+                                int x, int o, int e, const int* span);
+
 #ifdef __cplusplus
 }
 #endif
