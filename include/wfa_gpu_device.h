@@ -166,6 +166,10 @@ int wfagpu_amd_prime(wfagpu_amd_ctx_t* ctx);
  * per wave three uint64: s_memtime at arrival, s_memtime at release, (score << 32 | wavefront width - 1) -- and the number
  * of waves per workgroup of the launch that wrote them; *records = scores recorded (0 when nothing was). */
 void wfagpu_amd_debug_times(const wfagpu_amd_ctx_t* ctx, const void** d_records, unsigned int* records, int* waves);
+/* Diagnostics: which of the code objects that only some callers load this process has entered so far (launched, queried or
+ * primed a kernel of) -- bit 0: the ends-free wavefront kernels, bit 1: the two-piece wavefront kernels, bit 2: the two-piece
+ * backtrace kernels.  Process-wide, never cleared.  A gap-affine end-to-end caller reads 0. */
+unsigned int wfagpu_amd_debug_code_objects(void);
 
 /* The HIP stream (hipStream_t) the context runs on -- its own, or the one given at creation. */
 void* wfagpu_amd_stream(const wfagpu_amd_ctx_t* ctx);
@@ -232,6 +236,23 @@ int wfagpu_amd_align_device_span(wfagpu_amd_ctx_t* ctx, const wfagpu_amd_batch_t
  * search: a band that is asked for under a span is not used, said once on stderr).
  * NULL: end to end.  Negative members: rejected (-1, message), state unchanged. */
 int wfagpu_amd_configure_span(const wfagpu_amd_span_t* span);
+
+/* Two-piece (dual) gap-affine alignment, WFA2's gap_affine_2p: a gap of n bases costs
+ * min(gap_opening1 + n * gap_extension1, gap_opening2 + n * gap_extension2); match 0, all five members > 0 (WFA2's defaults:
+ * 4, 6, 2, 24, 1).  Scores and CIGARs are WFA2's; a CIGAR does not say which piece a gap used.  End to end, exact search
+ * (no band, no span). */
+typedef struct { int mismatch, gap_opening1, gap_extension1, gap_opening2, gap_extension2; } wfagpu_amd_penalties2p_t;
+
+/* wfagpu_amd_align_device under two-piece penalties; max_error is the score budget as there.  A member <= 0: -1. */
+int wfagpu_amd_align_device_2p(wfagpu_amd_ctx_t* ctx, const wfagpu_amd_batch_t* batch, const wfagpu_amd_penalties2p_t* penalties,
+                               int max_error, bool compute_cigar, int32_t* d_scores,
+                               const char** d_text, const unsigned long long** d_off, const unsigned int** d_len);
+
+/* Process-wide, like wfagpu_amd_configure_span: launch_alignments*, wfagpu_align and the CLI align with these two pieces; the
+ * affine_penalties_t they are handed is ignored (said once on stderr), a band that is asked for is not used (said once).
+ * NULL: back to gap-affine.  A member <= 0, or a span is configured: rejected (-1, message), state unchanged -- as is a span
+ * while two-piece penalties are configured. */
+int wfagpu_amd_configure_affine2p(const wfagpu_amd_penalties2p_t* penalties);
 
 void wfagpu_amd_last_stats(const wfagpu_amd_ctx_t* ctx, wfagpu_amd_stats_t* out);
 

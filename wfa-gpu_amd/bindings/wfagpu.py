@@ -82,6 +82,11 @@ class Span(C.Structure):  # wfagpu_amd_span_t: ends-free alignment, bases that m
                 ("text_end_free", C.c_int)]
 
 
+class Penalties2p(C.Structure):  # wfagpu_amd_penalties2p_t: a gap of n bases costs min(o1 + n e1, o2 + n e2)
+    _fields_ = [("mismatch", C.c_int), ("gap_opening1", C.c_int), ("gap_extension1", C.c_int), ("gap_opening2", C.c_int),
+                ("gap_extension2", C.c_int)]
+
+
 class Stats(C.Structure):  # wfagpu_amd_stats_t
     _fields_ = [("pack_ms", C.c_float), ("align_ms", C.c_float), ("trace_ms", C.c_float), ("total_ms", C.c_float),
                 ("align_launches", C.c_int), ("cells", C.c_ulonglong), ("arena_units", C.c_ulonglong),
@@ -107,6 +112,7 @@ ABI_SYMBOLS = [
     "wfagpu_amd_warmup", "wfagpu_amd_warmup_wait", "wfagpu_amd_last_launch_stats_device", "wfagpu_amd_debug_times",
     "wfagpu_host_pack_sequence", "wfagpu_host_pack_sequence_scalar", "wfagpu_host_pack_strip",
     "wfagpu_amd_align_device_span", "wfagpu_amd_configure_span",
+    "wfagpu_amd_align_device_2p", "wfagpu_amd_configure_affine2p", "wfagpu_amd_debug_code_objects",
 ]
 
 _lib = None
@@ -145,6 +151,13 @@ def load():
     lib.wfagpu_amd_align_device_span.restype = C.c_int
     lib.wfagpu_amd_configure_span.argtypes = [C.POINTER(Span)]
     lib.wfagpu_amd_configure_span.restype = C.c_int
+    lib.wfagpu_amd_align_device_2p.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Penalties2p), C.c_int, C.c_bool, C.c_void_p,
+                                               C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.wfagpu_amd_align_device_2p.restype = C.c_int
+    lib.wfagpu_amd_configure_affine2p.argtypes = [C.POINTER(Penalties2p)]
+    lib.wfagpu_amd_configure_affine2p.restype = C.c_int
+    lib.wfagpu_amd_debug_code_objects.argtypes = []
+    lib.wfagpu_amd_debug_code_objects.restype = C.c_uint
     lib.wfagpu_amd_last_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     lib.wfagpu_amd_last_stats.restype = None
     lib.wfagpu_amd_set_num_devices.argtypes = [C.c_int]
@@ -216,6 +229,18 @@ def configure_span(**kw):
         return
     if lib.wfagpu_amd_configure_span(C.byref(Span(**kw))) != 0:
         raise ValueError(f"wfagpu_amd_configure_span rejected {kw}")
+
+
+def configure_affine2p(pens=None):
+    """wfagpu_amd_configure_affine2p: launch_alignments*, wfagpu_align and the CLI align under the two-piece penalties
+    (x, o1, e1, o2, e2); the gap-affine penalties they are handed are ignored.  None: gap-affine again.  Raises ValueError when the
+    library rejects them (a member <= 0, or a span is configured)."""
+    lib = load()
+    if pens is None:
+        lib.wfagpu_amd_configure_affine2p(None)
+        return
+    if lib.wfagpu_amd_configure_affine2p(C.byref(Penalties2p(*[int(v) for v in pens]))) != 0:
+        raise ValueError(f"wfagpu_amd_configure_affine2p rejected {tuple(pens)}")
 
 
 def last_launch_stats():
@@ -476,13 +501,15 @@ class DeviceAligner:
         return d_packed.cpu().numpy().view(np.uint32), d_flags.cpu().numpy()
 
     def align(self, batch, penalties, max_error, compute_cigar, band=-1, band_width=0, fetch=True, d_scores=None, span=None,
-              fetch_ends=False):
+              fetch_ends=False, affine2p=None):
         """Returns (scores ndarray, cigars list or None).  With fetch=False results stay on the device
         and (d_scores tensor, (text_ptr, off_ptr, len_ptr)) is returned.  d_scores: the caller's int32 device tensor for the scores
         (the C interface takes the caller's buffer: a loop of calls need not allocate one per call).
         span: a Span, a dict of its fields or a 4-tuple (pattern begin, pattern end, text begin, text end free): ends-free alignment
         (wfagpu_amd_align_device_span; exact search, a band is an error).  fetch_ends (span only): a third result, int32[n, 2] =
-        the start and end diagonals (k0, k1) of every pair (k0 is INT32_MIN in score-only calls)."""
+        the start and end diagonals (k0, k1) of every pair (k0 is INT32_MIN in score-only calls).
+        affine2p: (x, o1, e1, o2, e2), two-piece gap-affine penalties (wfagpu_amd_align_device_2p; exact end-to-end search: a band or a
+        span is an error); `penalties` is ignored then."""
         torch = self.torch
         dev = torch.device("cuda", self.device)
         n = batch.num_pairs
@@ -490,8 +517,10 @@ class DeviceAligner:
             d_scores = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         assert d_scores.dtype == torch.int32 and d_scores.numel() >= max(n, 1) and d_scores.is_cuda
         t, o, l = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        pen = Penalties(*penalties)
+        pen = Penalties(*penalties) if affine2p is None else Penalties(0, 0, 0)
         span = _as_span(span)
+        if affine2p is not None and (span is not None or (band > 0 and band_width > 0)):
+            raise ValueError("two-piece penalties are not combined with an ends-free span or the adaptive band")
         d_ends = None
         if span is not None:
             if band > 0 and band_width > 0:
@@ -501,7 +530,10 @@ class DeviceAligner:
         elif fetch_ends:
             raise ValueError("fetch_ends needs a span")
         self._inputs_ready()
-        if span is not None:
+        if affine2p is not None:
+            rc = self.lib.wfagpu_amd_align_device_2p(self.ctx, C.byref(batch), C.byref(Penalties2p(*[int(v) for v in affine2p])), int(max_error),
+                                                     bool(compute_cigar), d_scores.data_ptr(), C.byref(t), C.byref(o), C.byref(l))
+        elif span is not None:
             rc = self.lib.wfagpu_amd_align_device_span(self.ctx, C.byref(batch), pen, int(max_error), C.byref(span), bool(compute_cigar),
                                                        d_scores.data_ptr(), d_ends.data_ptr() if d_ends is not None else None,
                                                        C.byref(t), C.byref(o), C.byref(l))
@@ -510,7 +542,7 @@ class DeviceAligner:
                                                   bool(compute_cigar), d_scores.data_ptr(), C.byref(t), C.byref(o),
                                                   C.byref(l))
         if rc != 0:
-            raise RuntimeError(f"wfagpu_amd_align_device{'_span' if span is not None else ''} failed ({rc})")
+            raise RuntimeError(f"wfagpu_amd_align_device{'_2p' if affine2p is not None else '_span' if span is not None else ''} failed ({rc})")
         if not fetch:
             res = (d_scores[:n], (t.value, o.value, l.value))
             return res + (d_ends[:n],) if fetch_ends else res

@@ -2,6 +2,7 @@
 // Textually included in the body of wfa_align_kernel (../align_kernel.hip), where every name used here is declared.
 // Reads: the ring rows handed in (rb_*: M[s-x], M[s-o-e], I/D[s-e]), Pw / Tw, plen, tlen, tid, NT.  Writes: the rows of score s (wb_*), one origin
 // byte per cell (codes), my_over (a value ran past a sequence end), wave_touch (an M cell sits on a sequence end).
+// TWOPIECE: also reads rb2_mo / rb2_ie / rb2_de (M[s-o2-e2], I2 / D2[s-e2]) and writes wb2_i / wb2_d, which the score step sets in front of the call.
       // ---- the cells of one score.  Lanes past the end recompute cell `hi` (same values, same
       // addresses), so no store needs an exec mask.  The vector ALU is the unit this kernel saturates (one
       // integer wave64 instruction holds its SIMD for 4 cycles), so everything uniform is folded into scalar
@@ -24,8 +25,25 @@
           const int k = min(k0 + tid, hi);
           // recurrences (wavefront_compute_affine.c:66-84)
           int ins, del, mv0;
+          int ins2 = 0, del2 = 0;       // (TWOPIECE: ins and del are I1 and D1, these I2 and D2)
           uint32_t code = 0;
-          {
+          if constexpr (TWOPIECE) {
+            // recurrences of the two pieces (wavefront_compute_affine2p.c:46-106): seven reads.  rb2_mo[k] = M[s-o2-e2][k-1],
+            // rb2_mo[k+2] = M[s-o2-e2][k+1], rb2_ie[k] = I2[s-e2][k-1], rb2_de[k] = D2[s-e2][k+1] (set by the score step)
+            const int m_x = (int)rb_mx[k];
+            const int m_ol = (int)rb_mo[k], m_or = (int)rb_mo[k + 2], i_e = (int)rb_ie[k], d_e = (int)rb_de[k];
+            const int m2_ol = (int)rb2_mo[k], m2_or = (int)rb2_mo[k + 2], i2_e = (int)rb2_ie[k], d2_e = (int)rb2_de[k];
+            ins = max(m_ol, i_e) + 1; ins2 = max(m2_ol, i2_e) + 1;
+            del = max(m_or, d_e); del2 = max(m2_or, d2_e);
+            const int mis = m_x + 1;
+            mv0 = max(max(del, del2), max(mis, max(ins, ins2)));
+            if constexpr (BT) {
+              // extension wins over opening on equal offsets (wavefront_compute_affine2p.c:173,191,214,232); M on equal offsets:
+              // mismatch, D2, D1, I2, I1 (:251-270, the last assignment stands; wavefront_backtrace.c:49-59)
+              code = (i_e >= m_ol ? BT2_I1_EXT : 0u) | (d_e >= m_or ? BT2_D1_EXT : 0u) | (i2_e >= m2_ol ? BT2_I2_EXT : 0u) | (d2_e >= m2_or ? BT2_D2_EXT : 0u);
+              code |= (mis == mv0) ? BT2_M_X : (del2 == mv0) ? BT2_M_D2 : (del == mv0) ? BT2_M_D1 : (ins2 == mv0) ? BT2_M_I2 : BT2_M_I1;
+            }
+          } else {
             int m_x, m_ol, m_or, i_e, d_e;
             if constexpr (BANDED) {
               auto rd = [&](const OffT* base, const int idx, const int kk, const int w) -> int {
@@ -63,6 +81,7 @@
           // below.  Everywhere else "invalid" means negative, which already reads as NULL, so the
           // computed limits can stand in for the trimmed ones.
           if constexpr (!LEAN) my_over |= (ins > tlen) || (del - k > plen);
+          if constexpr (TWOPIECE) my_over |= (ins2 > tlen) || (del2 - k > plen);
           // extend = longest common prefix from (v,h) (wavefront_extend.c:174-199), PER symbols per step.  No exec
           // mask for the cells that are not valid: a wave instruction costs the same with any lane active, mask
           // bookkeeping costs scalar instructions, and LDS reads at their meaningless addresses are harmless (an
@@ -118,6 +137,7 @@
           wb_m[k] = (OffT)mv;
           if constexpr (LEAN) wb_i[k] = (OffT)ins; else wb_i[k] = off_store<OffT>(ins);
           wb_d[k] = (OffT)del;
+          if constexpr (TWOPIECE) { wb2_i[k] = off_store<OffT>(ins2); wb2_d[k] = (OffT)del2; }
           // (TILED: `codes` is the tile row of the score, the byte of diagonal k sits tile_off(k) into it)
           if constexpr (BT) { if constexpr (TILED) codes[tile_off(k)] = (uint8_t)code; else codes[(uint32_t)(k - lo)] = (uint8_t)code; }
         }

@@ -64,6 +64,7 @@
 //   align/loop_lean_any.inc   lean score loop, gap extension > 1: superset limits from two counters (round 6)
 //   align/loop_lean_hbm.inc   lean score loop of the tiers whose ring lives in HBM
 //   align/loop_careful.inc    the careful score step (WFA2 to the letter)
+//   align/loop_careful_2p.inc the careful score step of the two-piece instantiations
 //   align/band_window.inc, align/loop_banded.inc   the adaptive band: the reference's window rule, the banded search
 #include <type_traits>
 
@@ -158,6 +159,19 @@ template <int NW> struct RowBook {
   }
 };
 
+// (TWOPIECE) the limits of I2 and D2 per score: the two words RowBook keeps for I and D, once more, the same way
+template <int NW> struct RowBook2 {
+  int i, d;             // NW == 1
+  int *I, *D;           // NW > 1 (LDS)
+  __device__ __forceinline__ int get_i(int slot) const { if constexpr (NW == 1) return __builtin_amdgcn_readlane(i, slot); else return I[slot]; }
+  __device__ __forceinline__ int get_d(int slot) const { if constexpr (NW == 1) return __builtin_amdgcn_readlane(d, slot); else return D[slot]; }
+  __device__ __forceinline__ void reset() { i = d = ROW_NONE_A; }
+  __device__ __forceinline__ void set(int slot, int vi, int vd) {
+    if constexpr (NW == 1) { const bool mine = (int)(threadIdx.x & 63) == slot; i = mine ? vi : i; d = mine ? vd : d; }
+    else { I[slot] = vi; D[slot] = vd; }
+  }
+};
+
 // Kernel arguments that are only needed between alignments (work list, result arrays, arena
 // bookkeeping) are re-read from the kernarg segment where they are used instead of being held in
 // SGPRs across the score loop: the loop needs every scalar register it can get (spilled SGPRs come
@@ -182,11 +196,17 @@ __device__ __forceinline__ ColdParams cold_params() {
 // the first row / column and end anywhere on the free part of the last ones (WFA2's alignment_endsfree).  Score 0 is a row of
 // diagonals, every score's extended M row is scanned for the lowest diagonal that satisfies WFA2's termination, the diagonal it
 // ended on goes to WfaAlignParams::ends; careful loop only, origin bytes in ROWS.  Everything else is the end-to-end kernel.
-template <int NW, bool BT, typename OffT, bool GLOBAL_RING, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool TIMED = false, bool ENDSFREE = false>
+// TWOPIECE (align_kernel_2p.hip includes this file for those instantiations): WFA2's gap_affine_2p -- a gap of n bases costs
+// min(o1 + n e1, o2 + n e2).  Five components per score (M, I1, D1, I2, D2): e2 + 1 rows each of I2 and D2 behind the D ring, a second
+// row book for their limits, seven reads and five stores per cell, origin bytes BT2_* (wfa_device.h); a score step of its own
+// (align/loop_careful_2p.inc: the careful one, WFA2 to the letter), origin bytes in ROWS.  Window and reach: below, where they are derived.
+template <int NW, bool BT, typename OffT, bool GLOBAL_RING, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool TIMED = false, bool ENDSFREE = false,
+          bool TWOPIECE = false>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu((NW == 1 && !BANDED) ? WPE : 1, 8)))
 wfa_align_kernel(const WfaAlignParams p) {
   static_assert(!HYBRID || (!GLOBAL_RING && !BANDED), "the hybrid ring is an exact LDS tier");
   static_assert(!ENDSFREE || (!BANDED && !HYBRID && !TIMED), "ends-free: the exact search of tiers 0, 1, 2 and 3");
+  static_assert(!TWOPIECE || (!BANDED && !HYBRID && !TIMED && !ENDSFREE), "two pieces: the end-to-end exact search of tiers 0, 1, 2 and 3");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NT = NW * 64;
   const int tid = threadIdx.x;
@@ -213,9 +233,11 @@ wfa_align_kernel(const WfaAlignParams p) {
   // of one bump-allocated row per score behind a row table (wfa_device.h).  The backward walk of a 1 kbp alignment then touches ~35
   // cache lines instead of 74 (55 origin bytes on 55 lines + 19 lines of row table: wfa_walk_kernel is bound by random 64-byte
   // accesses), and a score of the lean loops neither sizes, claims nor records a row: no refill test, no row-table entry.
-  constexpr bool TILED = BT && HOT && !HYBRID && NW == 1 && !BANDED && !ENDSFREE;      // (ends-free: ROWS in every tier)
+  constexpr bool TILED = BT && HOT && !HYBRID && NW == 1 && !BANDED && !ENDSFREE && !TWOPIECE;      // (ends-free, two pieces: ROWS in every tier)
   const int GZ = BANDED ? 4 * dm + 2 : 0;
   const int x = p.x, oe = p.oe, e = p.e;
+  // (TWOPIECE) the second piece; ring rows in all: dm of M, de each of I1 and D1, de2 each of I2 and D2
+  const int oe2 = TWOPIECE ? p.oe2 : 0, e2 = TWOPIECE ? p.e2 : 0, de2 = TWOPIECE ? p.de2 : 0;
 
   // ---- carve LDS -----------------------------------------------------------------------------
   unsigned char* sp = smem;
@@ -225,7 +247,7 @@ wfa_align_kernel(const WfaAlignParams p) {
   } else {
     Mr = reinterpret_cast<OffT*>(sp);
     // (HM_ROW: one more row, min(plen + k, tlen) per diagonal k -- how far a run on k can go)
-    sp += (((size_t)(dm + (HYBRID ? 1 : 2) * de + (HM_ROW ? 1 : 0)) * rs * sizeof(OffT)) + 15) & ~(size_t)15;
+    sp += (((size_t)(dm + (HYBRID ? 1 : 2) * de + 2 * de2 + (HM_ROW ? 1 : 0)) * rs * sizeof(OffT)) + 15) & ~(size_t)15;
   }
   OffT* const Dg = HYBRID ? reinterpret_cast<OffT*>(static_cast<char*>(p.gring) + (size_t)blockIdx.x * p.gring_stride) : nullptr;   // the D ring
   uint32_t* Pw = reinterpret_cast<uint32_t*>(sp);
@@ -248,6 +270,11 @@ wfa_align_kernel(const WfaAlignParams p) {
   book.reset();
   if constexpr (BOOK_NW == 1) { book.A = book.I = book.D = nullptr; }
   else { book.A = reinterpret_cast<int*>(bslot + 2); book.I = book.A + (bkm + 1); book.D = book.I + (bkm + 1); }
+  // (TWOPIECE) the limits of I2 and D2: two words more per score, behind the first book's
+  RowBook2<BOOK_NW> book2;
+  book2.reset();
+  if constexpr (BOOK_NW == 1 || !TWOPIECE) { book2.I = book2.D = nullptr; }
+  else { book2.I = book.D + (bkm + 1); book2.D = book2.I + (bkm + 1); }
 
   uint32_t chunk_cur = 0, chunk_left = 0;   // arena units owned by this block
   uint32_t dbg_i = 0;                       // (TIMED: barrier records written by this wave so far)
@@ -319,12 +346,24 @@ wfa_align_kernel(const WfaAlignParams p) {
     {
       // no optimal alignment costs more than min(P,T) mismatches plus one gap of |T - P| (that alignment
       // always exists); it bounds the backtrace row table
-      const long long worst = (long long)x * min(plen, tlen) + (kend ? oe + (long long)e * (abs(kend) - 1) : 0);
+      long long worst = (long long)x * min(plen, tlen) + (kend ? oe + (long long)e * (abs(kend) - 1) : 0);
+      if constexpr (TWOPIECE) worst = (long long)x * min(plen, tlen) + wfa_gap2p(abs(kend), oe, e, oe2, e2);
       budget = (int)min((long long)budget, worst);
     }
     int wlo = -plen, whi = tlen;
     bool feasible = true;
-    if constexpr (ENDSFREE) {
+    if constexpr (TWOPIECE) {
+      // Two pieces.  A gap of n bases costs g(n) = min(o1 + n e1, o2 + n e2), and g is subadditive (wfa_device.h), so a path that visits a
+      // diagonal t beyond both 0 and kend holds gaps of at least t + |kend| bases in one direction and t in the other:
+      // g(t + |kend|) + g(t) <= S.  The largest such t (wfa_stray2p: a bisection on the scalar unit, once per alignment) on either side
+      // of [min(0, kend), max(0, kend)] is the window; feasible: g(|kend|) <= S.
+      if (budget < INT_MAX / 2) {
+        const int ak = kend < 0 ? -kend : kend;
+        feasible = wfa_gap2p(ak, oe, e, oe2, e2) <= (long long)budget;
+        const int t = feasible ? wfa_stray2p(budget, ak, oe, e, oe2, e2) : 0;
+        whi = min(max(0, kend) + t, tlen); wlo = max(min(0, kend) - t, -plen);
+      }
+    } else if constexpr (ENDSFREE) {
       // Ends-free: a path starts on a diagonal a of S = [-pbf, tbf] and ends on a diagonal b of E = [kend - tef, kend + pef].  One that
       // visits k above both needs k - a bases of insertion and k - b of deletion in at least one gap each: 2o + (2k - a - b) e, largest
       // reach at a = tbf, b = kend + pef; below both, symmetric.  Between the hulls' ends every diagonal stays.  With a span of zeros
@@ -408,7 +447,7 @@ wfa_align_kernel(const WfaAlignParams p) {
         // with, so reads next to a row's ends need no predicate and no per-score guard fill.  It starts
         // here (rows of M, I, D are contiguous) and is kept by clearing, whenever a row is overwritten,
         // what the previous occupant of its slot had beyond the new limits.
-        const int cells = (dm + (HYBRID ? 1 : 2) * de) * rs;     // rs is even
+        const int cells = (dm + (HYBRID ? 1 : 2) * de + 2 * de2) * rs;     // rs is even
         if constexpr (sizeof(OffT) == 2) {
           uint32_t* w = reinterpret_cast<uint32_t*>(Mr);
           for (int i = tid; i < (cells >> 1); i += NT) w[i] = 0x80008000u;
@@ -426,6 +465,10 @@ wfa_align_kernel(const WfaAlignParams p) {
       }
       if constexpr (BOOK_NW == 1) book.reset();
       else { for (int i = tid; i <= bkm; i += NT) { book.A[i] = book.I[i] = book.D[i] = ROW_NONE_A; } }
+      if constexpr (TWOPIECE) {
+        if constexpr (BOOK_NW == 1) book2.reset();
+        else { for (int i = tid; i <= bkm; i += NT) { book2.I[i] = book2.D[i] = ROW_NONE_A; } }
+      }
       if constexpr (NW > 1) { if (tid < 24) red[tid] = (tid & 7) == 6 ? 0 : (((tid & 7) & 1) ? INT_MIN : INT_MAX); }
       block_sync<NW>();
 
@@ -527,6 +570,7 @@ wfa_align_kernel(const WfaAlignParams p) {
       }
       if constexpr (!ENDSFREE) {
         book.set(0, pack_range(0, 0), ROW_NONE_A, ROW_NONE_A);
+        if constexpr (TWOPIECE) book2.set(0, ROW_NONE_A, ROW_NONE_A);
         d0 = block_bcast<NW>(d0, bslot);
         done = (d0 & 1u) != 0;
       }
@@ -546,15 +590,29 @@ wfa_align_kernel(const WfaAlignParams p) {
       auto d_of = [&](OffT* ip) -> OffT* { return d_first + (ip - i_first); };
       OffT* p_m = m_first; OffT* p_x = m_first + (dm - x) * rs; OffT* p_oe = m_first + (dm - oe) * rs;
       OffT* p_ic = i_first; OffT* p_ip = i_first + (de - e) * rs;
+      // (TWOPIECE) the I2 ring behind the D ring, the D2 ring behind it; the M row of s-(o2+e2), the I2 rows of s and s-e2; and the rows
+      // of the second piece that cells_of_score reads and writes (set by the score step in front of every call)
+      OffT* const i2_first = TWOPIECE ? d_first + de * rs : nullptr;
+      OffT* const i2_end = TWOPIECE ? i2_first + de2 * rs : nullptr;
+      auto d2_of = [&](OffT* ip) -> OffT* { return ip + de2 * rs; };
+      OffT* p_oe2 = TWOPIECE ? m_first + (dm - oe2) * rs : nullptr;
+      OffT* p_ic2 = i2_first; OffT* p_ip2 = TWOPIECE ? i2_first + (de2 - e2) * rs : nullptr;
+      const OffT* rb2_mo = nullptr; const OffT* rb2_ie = nullptr; const OffT* rb2_de = nullptr;
+      OffT* wb2_i = nullptr; OffT* wb2_d = nullptr;
       // From a cell of score s on diagonal k the end is at least |k - kend| more gap bases away (an I or
       // D cell may sit inside the gap that is already open, so no opening cost can be assumed), so within
       // the budget only |k - kend| <= (budget - s) / e can still matter (exact, same argument as the
       // window).  [rlo, rhi] is that interval; it loses a diagonal on each side whenever the quotient
       // drops, tracked through the remainder reach_r without a division per score.
+      // (TWOPIECE) the same with the smaller of the two extensions: a cell of I1 (I2, D1, D2) sits inside an open gap of its piece and
+      // reaches the end |k - kend| bases away for no less than |k - kend| min(e1, e2) -- by going on in its piece, or by closing and
+      // opening the other one.  g(|k - kend|) would be the bound for M cells alone: under (4,6,2,24,1) and a budget of 20 the gap of five
+      // insertions to kend = 5 (cost 16) passes I1[8][1], four diagonals from the end with 12 left, where g(4) = 14.
+      const int e_reach = TWOPIECE ? min(e, e2) : e;
       const bool bounded = budget < INT_MAX / 2;
-      int reach_r = bounded ? budget % e : INT_MAX;
+      int reach_r = bounded ? budget % e_reach : INT_MAX;
       // (ENDSFREE: around the interval of end diagonals [kend - tef, kend + pef])
-      int rlo = bounded ? kend - tef - budget / e : INT_MIN / 2, rhi = bounded ? kend + pef + budget / e : INT_MAX / 2;
+      int rlo = bounded ? kend - tef - budget / e_reach : INT_MIN / 2, rhi = bounded ? kend + pef + budget / e_reach : INT_MAX / 2;
       // Number of consecutive scores up to s-1 whose wavefront exists with all three components and
       // untrimmed limits.  Once that covers every row the recurrences read, the limits follow from the M
       // limits alone and none of the "no wavefront" cases of wavefront_compute.c:41-71 can occur.
@@ -600,14 +658,18 @@ wfa_align_kernel(const WfaAlignParams p) {
       // on the border), and only such a cell can be the final one.  Until then the lean path needs neither the
       // per-cell overrun tests nor the per-score termination read.
       // (ENDSFREE: the careful loop only -- a row of score 0 that starts on the borders has touched them)
-      bool touched_ever = ENDSFREE || touched_at_0 || cold_params()->no_lean != 0;    // (WFAGPU_NO_LEAN: the lean path is never entered)
+      bool touched_ever = ENDSFREE || TWOPIECE || touched_at_0 || cold_params()->no_lean != 0;    // (WFAGPU_NO_LEAN: the lean path is never entered)
       // ---- score loop ----------------------------------------------------------------------------
       if (!done && status == WFA_ST_DONE) for (;;) {
-        #include "align/loop_banded.inc"
-        #include "align/loop_lean_e1.inc"
-        #include "align/loop_lean_any.inc"
-        #include "align/loop_lean_hbm.inc"
-        #include "align/loop_careful.inc"
+        if constexpr (TWOPIECE) {
+          #include "align/loop_careful_2p.inc"
+        } else {
+          #include "align/loop_banded.inc"
+          #include "align/loop_lean_e1.inc"
+          #include "align/loop_lean_any.inc"
+          #include "align/loop_lean_hbm.inc"
+          #include "align/loop_careful.inc"
+        }
       }
       if constexpr (BT) {
         if (status == WFA_ST_DONE) {
@@ -636,9 +698,9 @@ wfa_align_kernel(const WfaAlignParams p) {
   }
 }
 
-template <int NW, bool BT, typename OffT, bool GR, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool TIMED = false, bool EF = false>
+template <int NW, bool BT, typename OffT, bool GR, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool TIMED = false, bool EF = false, bool TP = false>
 void launch_inst(const WfaAlignParams& p, size_t lds, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
-  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE, TIMED, EF>;
+  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE, TIMED, EF, TP>;
   // the opt-in for large dynamic LDS is sticky per device and per kernel: pay the driver call once
   static thread_local size_t allowed[16] = {0};
   int dev = 0;
@@ -650,9 +712,9 @@ void launch_inst(const WfaAlignParams& p, size_t lds, int grid, hipStream_t stre
   wfa_launch_timed(k, dim3(grid), dim3(NW * 64), lds, stream, ev0, ev1, p);
 }
 
-template <int NW, bool BT, typename OffT, bool GR, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool EF = false>
+template <int NW, bool BT, typename OffT, bool GR, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool EF = false, bool TP = false>
 int occ_inst(size_t lds) {
-  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE, false, EF>;
+  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE, false, EF, TP>;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   int nb = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), NW * 64, lds) != hipSuccess) {
@@ -662,7 +724,49 @@ int occ_inst(size_t lds) {
   return nb;
 }
 
-#ifdef WFA_ALIGN_ENDSFREE_UNIT
+#if defined(WFA_ALIGN_TWOPIECE_UNIT)
+// ---- the two-piece translation unit (align_kernel_2p.hip): tiers 0, 1, 2 and 3, with and without backtrace, packed and byte-compare
+template <bool BT, bool RAW>
+void launch_tier_2p(const WfaAlignParams& p, int tier, size_t lds, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  switch (tier) {
+    case 0: launch_inst<1, BT, int16_t, false, RAW, false, false, 8, false, false, true>(p, lds, grid, stream, ev0, ev1); break;
+    case 1: launch_inst<4, BT, int16_t, false, RAW, false, false, 8, false, false, true>(p, lds, grid, stream, ev0, ev1); break;
+    case 2: launch_inst<16, BT, int16_t, false, RAW, false, false, 8, false, false, true>(p, lds, grid, stream, ev0, ev1); break;
+    default:
+      if (p.ring16) launch_inst<16, BT, int16_t, true, RAW, false, false, 8, false, false, true>(p, lds, grid, stream, ev0, ev1);
+      else launch_inst<16, BT, int32_t, true, RAW, false, false, 8, false, false, true>(p, lds, grid, stream, ev0, ev1);
+      break;
+  }
+}
+template <bool BT, bool RAW>
+int occ_tier_2p(int tier, size_t lds) {
+  switch (tier) {
+    case 0: return occ_inst<1, BT, int16_t, false, RAW, false, false, 8, false, true>(lds);
+    case 1: return occ_inst<4, BT, int16_t, false, RAW, false, false, 8, false, true>(lds);
+    case 2: return occ_inst<16, BT, int16_t, false, RAW, false, false, 8, false, true>(lds);
+    default: return occ_inst<16, BT, int32_t, true, RAW, false, false, 8, false, true>(lds);
+  }
+}
+
+}  // namespace
+
+void wfa_launch_align_2p(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  wfa_unit_entered(WFA_UNIT_ALIGN_2P);
+  const size_t lds = wfa_align_lds_bytes(p, tier);
+  if (with_bt) { if (raw) launch_tier_2p<true, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_2p<true, false>(p, tier, lds, grid, stream, ev0, ev1); }
+  else { if (raw) launch_tier_2p<false, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_2p<false, false>(p, tier, lds, grid, stream, ev0, ev1); }
+}
+
+int wfa_align_2p_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds) {
+  wfa_unit_entered(WFA_UNIT_ALIGN_2P);
+  if (with_bt) return raw ? occ_tier_2p<true, true>(tier, lds) : occ_tier_2p<true, false>(tier, lds);
+  return raw ? occ_tier_2p<false, true>(tier, lds) : occ_tier_2p<false, false>(tier, lds);
+}
+
+// (this code object is loaded by the first launch of one of its kernels: wfagpu_amd_prime does that only under configured two-piece penalties)
+namespace { __global__ void k_prime_align_2p() {} }
+void wfa_prime_align_2p(hipStream_t stream) { wfa_unit_entered(WFA_UNIT_ALIGN_2P); hipLaunchKernelGGL(k_prime_align_2p, dim3(1), dim3(64), 0, stream); }
+#elif defined(WFA_ALIGN_ENDSFREE_UNIT)
 // ---- the ends-free translation unit (align_kernel_ef.hip): tiers 0, 1, 2 and 3, with and without backtrace, packed and byte-compare
 template <bool BT, bool RAW>
 void launch_tier_ef(const WfaAlignParams& p, int tier, size_t lds, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
@@ -689,19 +793,21 @@ int occ_tier_ef(int tier, size_t lds) {
 }  // namespace
 
 void wfa_launch_align_ef(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  wfa_unit_entered(WFA_UNIT_ALIGN_EF);
   const size_t lds = wfa_align_lds_bytes(p, tier);
   if (with_bt) { if (raw) launch_tier_ef<true, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_ef<true, false>(p, tier, lds, grid, stream, ev0, ev1); }
   else { if (raw) launch_tier_ef<false, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_ef<false, false>(p, tier, lds, grid, stream, ev0, ev1); }
 }
 
 int wfa_align_ef_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds) {
+  wfa_unit_entered(WFA_UNIT_ALIGN_EF);
   if (with_bt) return raw ? occ_tier_ef<true, true>(tier, lds) : occ_tier_ef<true, false>(tier, lds);
   return raw ? occ_tier_ef<false, true>(tier, lds) : occ_tier_ef<false, false>(tier, lds);
 }
 
 // (this code object is loaded by the first launch of one of its kernels: wfagpu_amd_prime does that only under a configured span)
 namespace { __global__ void k_prime_align_ef() {} }
-void wfa_prime_align_ef(hipStream_t stream) { hipLaunchKernelGGL(k_prime_align_ef, dim3(1), dim3(64), 0, stream); }
+void wfa_prime_align_ef(hipStream_t stream) { wfa_unit_entered(WFA_UNIT_ALIGN_EF); hipLaunchKernelGGL(k_prime_align_ef, dim3(1), dim3(64), 0, stream); }
 #else
 // tier -> instantiation (banded kernels exist for the packed LDS tiers only)
 template <bool BT, bool RAW>
@@ -776,11 +882,11 @@ int occ_tier_banded(int tier, size_t lds) {
 size_t wfa_align_lds_bytes(const WfaAlignParams& p, int tier) {
   size_t ring = 0;
   if (tier == 4) ring = (((size_t)(p.dm + p.de) * p.rs * sizeof(int16_t)) + 15) & ~(size_t)15;       // hybrid: M and I rings
-  else if (tier != 3) ring = (((size_t)(p.dm + 2 * p.de + ((tier == 0 && p.band_width <= 0) ? 1 : 0)) * p.rs * sizeof(int16_t)) + 15) & ~(size_t)15;     // (+ the run-limit row of the one-wave exact kernels)
+  else if (tier != 3) ring = (((size_t)(p.dm + 2 * p.de + 2 * p.de2 + ((tier == 0 && p.band_width <= 0) ? 1 : 0)) * p.rs * sizeof(int16_t)) + 15) & ~(size_t)15;     // (+ the run-limit row of the one-wave exact kernels)
   const size_t seq = (size_t)2 * p.seq_words_cap * 4;
   // reduction slots [24] + broadcast [2] + (NW > 1) row book [3][book]
   const size_t bk = (size_t)p.book_mask + 1;
-  const size_t meta = (size_t)(24 + 2 + ((tier == 0 || p.band_width > 0) ? 0 : 3 * bk)) * 4;     // (tiers 1, 2, 3, 4 of the exact search: row book in LDS)
+  const size_t meta = (size_t)(24 + 2 + ((tier == 0 || p.band_width > 0) ? 0 : (p.e2 > 0 ? 5 : 3) * bk)) * 4;     // (tiers 1, 2, 3, 4 of the exact search: row book in LDS; two pieces: I2 and D2 too)
   return ((ring + seq + meta) + 15) & ~(size_t)15;
 }
 

@@ -28,6 +28,16 @@
 
 namespace {
 
+// TRACE_2P: this translation unit is compiled twice.  As trace_kernel.hip it holds the gap-affine backtrace; trace_kernel_2p.hip
+// includes it with WFA_TRACE_TWOPIECE_UNIT set for the two-piece one (five walk states, origin bytes BT2_*, gap runs priced by the
+// cheaper piece) -- a code object of its own behind wfa_launch_trace_2p, loaded only by two-piece calls with CIGARs, so that the
+// gap-affine kernels carry none of it.
+#ifdef WFA_TRACE_TWOPIECE_UNIT
+constexpr bool TRACE_2P = true;
+#else
+constexpr bool TRACE_2P = false;
+#endif
+
 // How the replay reads a packed sequence: words i and i+1 at a time, at positions that only move forward.
 //   SeqDirect  the whole sequence is addressable (LDS copy, or global memory)
 //   SeqWindow  8 words per lane in LDS, refilled from global memory when the position leaves them: 64 bytes of LDS per
@@ -143,13 +153,18 @@ __device__ __forceinline__ int dec_digits(uint32_t n) {
 // wavefront kernel, k0 is where the walk arrives.
 struct PairEnds { int k0, k1; };
 
+// The penalties a replay prices its text with: gap-affine (e2 == 0), or two pieces -- a gap run of n bases costs
+// min(o + n e, o2 + n e2): a CIGAR does not say which piece a gap used.  Zeros: the replay only sizes the text.
+struct GapPens { int x, o, e, o2, e2; };
+__device__ __forceinline__ GapPens pens_of(const WfaTraceParams& p) { return GapPens{p.x, p.oe - p.e, p.e, p.oe2 - p.e2, p.e2}; }
+
 struct RleSink {
   char* out;      // nullptr: count only
   uint32_t cap;   // bytes available at `out` (items that would not fit are only counted)
   uint32_t len;
   uint32_t run;
   char op;
-  int x, o, e;    // penalties: the gap-affine cost of the emitted items is accumulated while writing
+  GapPens pen;    // penalties: the cost of the emitted items is accumulated while writing
   int cost;
   bool words;     // the slot at `out` is this lane's own up to `cap`: an item may be stored as one (unaligned) 32-bit word
   uint32_t free_run;   // bases of the current run that are free (ends-free alignment): printed, not priced
@@ -172,8 +187,11 @@ struct RleSink {
     }
     // (utils/verification.c:91-146 of the reference: a new gap wherever the operation changes)
     // (a free run merges with a paid gap of the same kind next to it: the gap is priced for its paid bases alone)
-    if (op == 'X') cost += x * (int)run;
-    else if (op != 'M' && run > free_run) cost += o + e * (int)(run - free_run);
+    if (op == 'X') cost += pen.x * (int)run;
+    else if (op != 'M' && run > free_run) {
+      const int n = (int)(run - free_run), c1 = pen.o + pen.e * n;
+      if constexpr (TRACE_2P) cost += min(c1, pen.o2 + pen.e2 * n); else cost += c1;
+    }
     len += (uint32_t)nd + 1;
     run = 0; free_run = 0;
   }
@@ -192,9 +210,9 @@ struct RleSink {
 // (OPS_LDS: the op list is in LDS -- said explicitly, a pointer that was global or LDS by a run-time choice loads with flat_load)
 template <bool RAW, bool OPS_LDS = false, typename PV, typename TV>
 __device__ __forceinline__ uint32_t replay_views(const uint8_t* ops, uint32_t nops, PV& Pw, TV& Tw,
-                                                 int plen, int tlen, const PairEnds ends, char* out, int x, int o, int e, int* cost,
+                                                 int plen, int tlen, const PairEnds ends, char* out, const GapPens pen, int* cost,
                                                  uint32_t out_cap = 0xFFFFFFFFu, bool words = false) {
-  RleSink sink{out, out_cap, 0, 0, 0, x, o, e, 0, words, 0};
+  RleSink sink{out, out_cap, 0, 0, 0, pen, 0, words, 0};
   // (ends-free: the path starts on diagonal k0 at the border, behind the free bases of the sequence that sticks out)
   int v = max(-ends.k0, 0), h = max(ends.k0, 0);
   sink.push_free(ends.k0 > 0 ? 'I' : 'D', (uint32_t)(v + h));
@@ -236,10 +254,10 @@ __device__ __forceinline__ uint32_t replay_views(const uint8_t* ops, uint32_t no
 
 template <bool RAW, bool OPS_LDS = false>
 __device__ __forceinline__ uint32_t replay(const uint8_t* ops, uint32_t nops, const uint32_t* Pw, const uint32_t* Tw,
-                                           int plen, int tlen, const PairEnds ends, char* out, int x, int o, int e, int* cost,
+                                           int plen, int tlen, const PairEnds ends, char* out, const GapPens pen, int* cost,
                                            uint32_t out_cap = 0xFFFFFFFFu, bool words = false) {
   SeqDirect pv{Pw}, tv{Tw};
-  return replay_views<RAW, OPS_LDS>(ops, nops, pv, tv, plen, tlen, ends, out, x, o, e, cost, out_cap, words);
+  return replay_views<RAW, OPS_LDS>(ops, nops, pv, tv, plen, tlen, ends, out, pen, cost, out_cap, words);
 }
 
 constexpr int TRACE_THREADS = 64;
@@ -293,7 +311,31 @@ __device__ __forceinline__ void fetch_bt_rows(const WfaTraceParams& p, const BtB
 // (Gap open or extension as selects, said explicitly: the compiler made them of the branches the kernels had written out, and does
 // not once the paths of this function meet in its return value -- 3.5 % of the wave kernel's time.)
 constexpr uint32_t OP_NONE = 0;
+// Two pieces (TRACE_2P, origin bytes BT2_*): five states -- 0: M, 1: I1, 2: D1, 3: I2, 4: D2 -- and the score steps x, e1, o1 + e1, e2,
+// o2 + e2 (wavefront_backtrace.c:354-415).  In M the byte names the component the offset came from; inside a gap component its flag
+// says whether the extension won, or tied, against the opening.  The operations stay X / I / D.
+// (one walk step per translation unit: the unit macro selects its body)
 __device__ __forceinline__ uint32_t walk_step(const uint32_t code, int& state, int& s, int& k, const WfaTraceParams& p) {
+#ifdef WFA_TRACE_TWOPIECE_UNIT
+  uint32_t after = 0;
+  int st = state;
+  if (st == 0) {
+    const uint32_t org = code & BT2_M_MASK;
+    if (org == BT2_M_X) { s -= p.x; return OP_X | OP_EXT_AFTER; }
+    if (org == BT2_M_NONE || org > BT2_M_X) return OP_NONE;
+    st = (int)(org >> 4);      // (BT2_M_I1 .. BT2_M_D2 are the states 1, 3, 2, 4 in the order I1, I2, D1, D2)
+    st = st == 2 ? 3 : (st == 3 ? 2 : st);
+    after = OP_EXT_AFTER;
+  }
+  // a gap component: its own extension or its opening
+  const bool second = st >= 3, is_d = (st & 1) == 0;
+  const uint32_t flag = second ? (is_d ? BT2_D2_EXT : BT2_I2_EXT) : (is_d ? BT2_D1_EXT : BT2_I1_EXT);
+  const bool ext = (code & flag) != 0;
+  s -= second ? (ext ? p.e2 : p.oe2) : (ext ? p.e : p.oe);
+  k += is_d ? 1 : -1;
+  state = ext ? st : 0;
+  return (is_d ? OP_D : OP_I) | after;
+#else
   uint32_t op;
   const bool i_ext = (code & BT_I_EXT) != 0, d_ext = (code & BT_D_EXT) != 0;
   if (state == 0) {
@@ -308,6 +350,7 @@ __device__ __forceinline__ uint32_t walk_step(const uint32_t code, int& state, i
     op = OP_D; ++k; s -= d_ext ? p.e : p.oe; state = d_ext ? 2 : 0;
   }
   return op;
+#endif
 }
 // The span of a walk: it starts on diagonal k1 and may end on any diagonal of [k0_lo, k0_hi] (end to end: on tlen - plen and on 0).
 struct WalkSpan { int k1, k0_lo, k0_hi; };
@@ -504,7 +547,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_win_kernel(const WfaTr
   const PairEnds ends = stored_ends(p, pair, plen, tlen);
   uint32_t len = 0;
   if (active && !fail) {
-    len = replay_any(p.raw, q, nops, pv, tv, plen, tlen, ends, (char*)nullptr, 0, 0, 0, (int*)nullptr);
+    len = replay_any(p.raw, q, nops, pv, tv, plen, tlen, ends, (char*)nullptr, GapPens{}, (int*)nullptr);
     if (len == 0xFFFFFFFFu) fail = true;
   }
   const uint32_t need_txt = (active && !fail) ? len + 1u : 0u;
@@ -514,7 +557,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_win_kernel(const WfaTr
     if (!fail) {
       int cost = 0;
       pv.base = -1000; tv.base = -1000;
-      replay_any(p.raw, q, nops, pv, tv, plen, tlen, ends, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
+      replay_any(p.raw, q, nops, pv, tv, plen, tlen, ends, p.text + txt_off, pens_of(p), &cost);
       finish_pair(p, pair, false, txt_off, len, cost, p.score[pair]);
     } else finish_pair(p, pair, true);
   }
@@ -602,7 +645,7 @@ __global__ void __launch_bounds__(LANE_WAVES * 64) wfa_trace_lane_kernel(const W
   const uint8_t* const q = q_end - nops;
   uint32_t len = 0;
   if (active && !fail) {
-    len = replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, nullptr, 0, 0, 0, nullptr);
+    len = replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, nullptr, GapPens{}, nullptr);
     if (len == 0xFFFFFFFFu) fail = true;
   }
   const uint32_t need_txt = (active && !fail) ? len + 1u : 0u;
@@ -610,7 +653,7 @@ __global__ void __launch_bounds__(LANE_WAVES * 64) wfa_trace_lane_kernel(const W
   if (active && !fail && txt_off + need_txt > p.text_cap) fail = true;
   if (active) {
     int cost = 0;
-    if (!fail) replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
+    if (!fail) replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, p.text + txt_off, pens_of(p), &cost);
     finish_pair(p, pair, fail, txt_off, len, cost, score);
   }
 }
@@ -680,7 +723,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_kernel(const WfaTraceP
       uint32_t len = 0xFFFFFFFFu;
       int cost = 0;
       if (!fail) {
-        len = replay_any<OPS_LDS>(p.raw, OPS_LDS ? q_lds : q, nops, pv, tv, plen, tlen, ends, p.text_scratch + s_off, p.x, p.oe - p.e, p.e, &cost, bound, true);
+        len = replay_any<OPS_LDS>(p.raw, OPS_LDS ? q_lds : q, nops, pv, tv, plen, tlen, ends, p.text_scratch + s_off, pens_of(p), &cost, bound, true);
         if (len != 0xFFFFFFFFu && len + 1u > bound) len = 0xFFFFFFFFu;
       }
       // (cigar_off: the text's place in the scratch until the compaction)
@@ -691,7 +734,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_kernel(const WfaTraceP
   }
   uint32_t len = 0;
   if (active && !fail) {
-    len = replay_any(p.raw, q, nops, pv, tv, plen, tlen, ends, (char*)nullptr, 0, 0, 0, (int*)nullptr);
+    len = replay_any(p.raw, q, nops, pv, tv, plen, tlen, ends, (char*)nullptr, GapPens{}, (int*)nullptr);
     if (len == 0xFFFFFFFFu) fail = true;
   }
   const uint32_t need_txt = (active && !fail) ? len + 1u : 0u;
@@ -700,7 +743,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_emit_kernel(const WfaTraceP
   if (active) {
     if (!fail) {
       int cost = 0;
-      replay_any(p.raw, q, nops, pv, tv, plen, tlen, ends, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
+      replay_any(p.raw, q, nops, pv, tv, plen, tlen, ends, p.text + txt_off, pens_of(p), &cost);
       finish_pair(p, pair, false, txt_off, len, cost, p.score[pair]);
     } else finish_pair(p, pair, true);
   }
@@ -864,7 +907,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_wave_kernel(const Wfa
     uint32_t len = 0;
     int cost = 0;
     if (!fail) {
-      len = replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, lane == 0 ? text_lds : nullptr, p.x, p.oe - p.e, p.e, &cost, (uint32_t)p.text_lds_bytes);
+      len = replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, lane == 0 ? text_lds : nullptr, pens_of(p), &cost, (uint32_t)p.text_lds_bytes);
       if (len == 0xFFFFFFFFu) fail = true;
     }
     unsigned long long txt_off = 0;
@@ -879,7 +922,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_wave_kernel(const Wfa
         char* dst = p.text + txt_off;
         for (uint32_t i = lane; i <= len; i += 64) dst[i] = text_lds[i];
       } else {
-        replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, lane == 0 ? p.text + txt_off : nullptr, p.x, p.oe - p.e, p.e, &cost);
+        replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, lane == 0 ? p.text + txt_off : nullptr, pens_of(p), &cost);
       }
       if (lane == 0) {
         p.cigar_off[pair] = txt_off;
@@ -974,7 +1017,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_group_kernel(const Wf
     uint32_t len = 0;
     int cost = 0;
     if (active && !fail && sub == 0) {
-      len = replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, text_lds, p.x, p.oe - p.e, p.e, &cost, (uint32_t)p.text_lds_bytes);
+      len = replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, text_lds, pens_of(p), &cost, (uint32_t)p.text_lds_bytes);
     }
     len = __shfl(len, lead);
     if (active && !fail && len == 0xFFFFFFFFu) fail = true;
@@ -988,7 +1031,7 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_group_kernel(const Wf
         char* dst = p.text + txt_off;
         for (uint32_t i = sub; i <= len; i += L) dst[i] = text_lds[i];
       } else if (sub == 0) {
-        replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, p.text + txt_off, p.x, p.oe - p.e, p.e, &cost);
+        replay<RAW>(q, nops, Pw, Tw, plen, tlen, ends, p.text + txt_off, pens_of(p), &cost);
       }
     }
     if (active && sub == 0) finish_pair(p, pair, fail, txt_off, len, cost, score);
@@ -1030,7 +1073,12 @@ void launch_wave(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0, hi
 
 // ev0 / ev1: receive the start of the first and the end of the last kernel launched here (a call that launches nothing --
 // n_work == 0 -- leaves them alone: returns false)
+#ifdef WFA_TRACE_TWOPIECE_UNIT
+bool wfa_launch_trace_2p(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  wfa_unit_entered(WFA_UNIT_TRACE_2P);
+#else
 bool wfa_launch_trace(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+#endif
   if (p.n_work == 0) return false;
   if (p.wave_kernel && p.group > 1) {
     switch (p.group) {
@@ -1084,5 +1132,11 @@ bool wfa_launch_trace(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev
 
 // Loads this translation unit's code object on the current device (the runtime loads a code object at the first launch of
 // any of its kernels: 5-25 ms each): launch_alignments* call it while a cold call waits for its first upload.
+#ifdef WFA_TRACE_TWOPIECE_UNIT
+// (this code object is loaded by the first launch of one of its kernels: wfagpu_amd_prime does that only under configured two-piece penalties)
+namespace { __global__ void k_prime_trace_2p() {} }
+void wfa_prime_trace_2p(hipStream_t stream) { wfa_unit_entered(WFA_UNIT_TRACE_2P); hipLaunchKernelGGL(k_prime_trace_2p, dim3(1), dim3(64), 0, stream); }
+#else
 namespace { __global__ void k_prime_trace() {} }
 void wfa_prime_trace(hipStream_t stream) { hipLaunchKernelGGL(k_prime_trace, dim3(1), dim3(64), 0, stream); }
+#endif

@@ -52,6 +52,36 @@ enum : uint32_t {
 //   bit  1    D came from D (gap extension) rather than from M (gap open)
 //   bit  0    I came from I (gap extension) rather than from M (gap open)
 enum : uint32_t { BT_M_NONE = 0, BT_M_X = 12, BT_M_D = 8, BT_M_I = 4, BT_M_MASK = 12, BT_D_EXT = 2, BT_I_EXT = 1 };
+// Two-piece gap-affine (the TWOPIECE instantiations, align_kernel_2p.hip), 7 bits used:
+//   bits 6:4  source of M : 0 none, then by WFA2's priority on equal offsets (wavefront_backtrace.c:49-59: mismatch, D2, D1, I2, I1)
+//   bit  3    D2 came from D2 (extension won, or tied, against opening)      bit 2    I2 came from I2
+//   bit  1    D1 came from D1                                                bit 0    I1 came from I1
+enum : uint32_t { BT2_M_NONE = 0, BT2_M_X = 5u << 4, BT2_M_D2 = 4u << 4, BT2_M_D1 = 3u << 4, BT2_M_I2 = 2u << 4, BT2_M_I1 = 1u << 4, BT2_M_MASK = 7u << 4,
+                  BT2_D2_EXT = 8, BT2_I2_EXT = 4, BT2_D1_EXT = 2, BT2_I1_EXT = 1 };
+
+// Two-piece gap cost and what a budget affords (host and device).  A gap of n bases costs g(n) = min(o1 + n e1, o2 + n e2), g(0) = 0;
+// g is increasing, concave and subadditive (g(a) + g(b) >= g(a + b)): several gaps never cost less than one gap of their bases.
+// (oe1 = o1 + e1, oe2 = o2 + e2, as the kernels carry them)
+__host__ __device__ inline long long wfa_gap2p(const long long n, const int oe1, const int e1, const int oe2, const int e2) {
+  if (n <= 0) return 0;
+  const long long a = oe1 + (n - 1) * e1, b = oe2 + (n - 1) * e2;
+  return a < b ? a : b;
+}
+// R(S): the longest gap a budget S pays for (0: none)
+__host__ __device__ inline long long wfa_reach2p(const long long S, const int oe1, const int e1, const int oe2, const int e2) {
+  const long long a = S >= oe1 ? (S - oe1) / e1 + 1 : 0, b = S >= oe2 ? (S - oe2) / e2 + 1 : 0;
+  return a > b ? a : b;
+}
+// The largest t with g(t) + g(t + ak) <= S: how far beyond both its end diagonals (ak apart) a path of cost <= S can stray -- it
+// needs a gap of t + ak bases out and one of t back, or more gaps of no fewer bases.  (g(ak) <= S assumed: t = 0 qualifies.)
+__host__ __device__ inline int wfa_stray2p(const long long S, const long long ak, const int oe1, const int e1, const int oe2, const int e2) {
+  long long lo = 0, hi = wfa_reach2p(S / 2, oe1, e1, oe2, e2);      // (2 g(t) <= S bounds it)
+  while (lo < hi) {
+    const long long mid = lo + (hi - lo + 1) / 2;
+    if (wfa_gap2p(mid, oe1, e1, oe2, e2) + wfa_gap2p(mid + ak, oe1, e1, oe2, e2) <= S) lo = mid; else hi = mid - 1;
+  }
+  return (int)lo;
+}
 
 // Operations of a reversed op list (what the backward walk leaves for the replay): the kind, and whether a run of matches
 // follows the operation (re-derived by the replay as a longest common prefix).
@@ -130,6 +160,9 @@ struct WfaAlignParams {
   // kernel clamps each value to the pair's own sequence length -- and where the diagonal the alignment ended on goes
   int span_pbf, span_pef, span_tbf, span_tef;   // pattern begin / pattern end / text begin / text end free
   int32_t* ends;                 // [2 * pair + 1] out: end diagonal k1 ([2 * pair], the start diagonal k0, is the backtrace's; INT_MIN here)
+  // two-piece gap-affine (only the TWOPIECE instantiations, align_kernel_2p.hip, read these; e2 == 0: gap-affine): the second piece as
+  // open + extend and extend, e2 + 1 rows each of I2 and D2 behind the D ring.  x / oe / e / de are the first piece, dm = max(x, oe, oe2) + 1.
+  int oe2, e2, de2;
 };
 
 struct WfaTraceParams {
@@ -169,7 +202,7 @@ struct WfaTraceParams {
   char* text_scratch;
   unsigned long long text_scratch_cap;
   unsigned long long* scratch_top;
-  int min_op_cost;               // min(x, e): an alignment of score s has at most s / min_op_cost operations
+  int min_op_cost;               // min(x, e) (two pieces: min(x, e1, e2)): an alignment of score s has at most s / min_op_cost operations
   int item_chars;                // widest RLE item (digits of the longest sequence + 1): sizes the upper-bound text slots
   unsigned long long* cigar_off; // [pair] out: byte offset of the CIGAR in `text` (between walk and replay: of the op list in `ops`)
   uint32_t* cigar_len;           // [pair] out: strlen; 0xFFFFFFFF if it did not fit
@@ -180,6 +213,7 @@ struct WfaTraceParams {
   int span_pbf, span_tbf;
   int32_t* ends;
   int extra_items;               // RLE items a text may have beyond 2 * operations + 1 (the two free runs): sizes the upper-bound text slots
+  int oe2, e2;                   // two-piece gap-affine (wfa_launch_trace_2p only): the second piece; origin bytes are BT2_*
 };
 
 // Host-side launchers (one per translation unit).
@@ -216,7 +250,21 @@ void wfa_prime_align_ef(hipStream_t stream);
 // launch_alignments* -- wants its wfagpu_amd_align_device call to run under (nullptr: end to end), as four ints.
 bool wfa_configured_span(int* out4);
 const int* wfa_lane_span4();
+// The two-piece instantiations (align_kernel_2p.hip: a code object of their own, loaded only by two-piece calls): tiers 0, 1, 2 and 3,
+// exact search, careful loop, origin bytes in ROWS.  wfa_align_lds_bytes serves them too (WfaAlignParams::e2 > 0).
+void wfa_launch_align_2p(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream,
+                         hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+int wfa_align_2p_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds_bytes);
+void wfa_prime_align_2p(hipStream_t stream);
+// The penalties of wfagpu_amd_configure_affine2p (wfa_launch.hip): false when none are configured; out (optional) receives
+// {x, o1, e1, o2, e2}.  wfa_lane_affine2p5: what the calling thread -- a lane of launch_alignments* -- wants its
+// wfagpu_amd_align_device call to run under (nullptr: gap-affine), as five ints.
+bool wfa_configured_affine2p(int* out5);
+const int* wfa_lane_affine2p5();
 bool wfa_launch_trace(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);     // false: nothing to launch
+// (the backtrace of two-piece alignments: trace_kernel_2p.hip, the same kernels compiled for five walk states and BT2_* origin bytes)
+bool wfa_launch_trace_2p(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+void wfa_prime_trace_2p(hipStream_t stream);
 // Tier 5 (short_kernel.hip): 64 / lanes alignments per wavefront (lanes = 16 or 32 diagonals each), rings in registers; with_bt: one row
 // of `lanes` origin bytes per score for the backtrace.
 bool wfa_short_supported(int x, int oe, int e);
@@ -230,6 +278,11 @@ struct WfaShortEntry { void (*launch)(const WfaAlignParams&, int, hipStream_t, h
 const WfaShortEntry* wfa_short_entry_e2(int ascii, int bt, int l32, int idx);
 const WfaShortEntry* wfa_short_entry_e3(int ascii, int bt, int l32, int idx);
 const WfaShortEntry* wfa_short_entry_e4(int ascii, int bt, int l32, int idx);
+// Which of the optional code objects -- the ones only some callers load -- this process has entered: every host function that launches,
+// queries or primes a kernel of such a unit says so (the runtime loads a code object at the first of these).  Process-wide, never
+// cleared; wfagpu_amd_debug_code_objects() (wfa_host.hip) hands the bits out, tests check "never loaded" with them.
+enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u };
+void wfa_unit_entered(unsigned unit);
 // Code-object priming: one empty launch per kernel translation unit (see the definitions).
 void wfa_prime_pack(hipStream_t stream);
 void wfa_prime_align(hipStream_t stream);

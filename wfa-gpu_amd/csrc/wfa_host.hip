@@ -38,6 +38,11 @@ static_assert(sizeof(sequence_pair_t) == sizeof(WfaSeqPair), "ABI mirror");
     }                                                                                   \
   } while (0)
 
+// The optional code objects this process has entered (wfa_device.h: wfa_unit_entered; read by wfagpu_amd_debug_code_objects)
+#include <atomic>
+static std::atomic<unsigned> g_units_entered{0};
+void wfa_unit_entered(unsigned unit) { g_units_entered.fetch_or(unit, std::memory_order_relaxed); }
+
 // helper-kernel launch + launch-error check (the align/trace launchers are checked at their call sites)
 #define LAUNCH_K(kern, grid, block, lds, stream, ...)                 \
   do {                                                                 \
@@ -487,6 +492,8 @@ void wfagpu_amd_debug_times(const wfagpu_amd_ctx_t* c, const void** d_records, u
   if (waves) *waves = c ? c->dbg_waves : 0;
 }
 
+unsigned int wfagpu_amd_debug_code_objects(void) { return g_units_entered.load(std::memory_order_relaxed); }
+
 void wfagpu_amd_trim(wfagpu_amd_ctx_t* c) {
   if (!c || c->retired.empty()) return;
   hipSetDevice(c->device);
@@ -503,6 +510,7 @@ int wfagpu_amd_prime(wfagpu_amd_ctx_t* c) {
   wfa_prime_pack(c->stream);
   wfa_prime_short(c->stream);
   if (wfa_configured_span(nullptr)) wfa_prime_align_ef(c->stream);      // (the ends-free kernels: only callers under a span load them)
+  if (wfa_configured_affine2p(nullptr)) { wfa_prime_align_2p(c->stream); wfa_prime_trace_2p(c->stream); }  // (the two-piece kernels: only callers under such penalties)
   LAUNCH_K(k_iota, dim3(1), dim3(64), 0, c->stream, static_cast<uint32_t*>(nullptr), 0u, 0u);      // (this file's)
   HIP_TRY(hipGetLastError());
   c->primed = true;
@@ -535,6 +543,16 @@ int window_width(long long S, int o, int e, unsigned max_seq_len) {
   const long long all = 2ll * max_seq_len + 1;
   if (S >= INT_MAX / 2) return (int)all;
   return (int)std::max<long long>(1, std::min<long long>(all, (S - o) / e + 1));
+}
+
+// The same for two pieces (the kernel's window: g(t + |kend|) + g(t) <= S on either side of the end diagonals).  |kend| + 2 t + 1 does
+// not shrink as |kend| grows (g is concave: t gives way by at most half a diagonal per diagonal of |kend|), and at the largest |kend| a
+// budget affords, R(S), t is 0: R(S) + 1 diagonals, two more for the rounding of t.  A bound, not an exact figure: a pair whose own
+// window is wider comes back as a BAND failure and is escalated like any other.
+int window_width_2p(long long S, const WfaAlignParams& p, unsigned max_seq_len) {
+  const long long all = 2ll * max_seq_len + 1;
+  if (S >= INT_MAX / 2) return (int)all;
+  return (int)std::max<long long>(1, std::min<long long>(all, wfa_reach2p(S, p.oe, p.e, p.oe2, p.e2) + 3));
 }
 
 // Smallest tier whose LDS footprint fits a score budget S.
@@ -581,8 +599,9 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   // Ends-free (p.ends): the window is the end-to-end one around the hull of the start and end diagonals -- wider by at most the
   // free bases (clamped to the sequences).  A bound for the longest pair, not an exact figure: a pair whose own window is wider
   // comes back as a BAND failure and is escalated like any other.  Tiers 0, 1, 2 and 3 only.
-  const bool ef = p.ends != nullptr;
-  int width = window_width(max_score, p.oe - p.e, p.e, max_seq_len);
+  // Two pieces (p.e2 > 0): tiers 0, 1, 2 and 3 of the exact search, like ends-free; never combined with it.
+  const bool ef = p.ends != nullptr, tp2 = p.e2 > 0;
+  int width = tp2 ? window_width_2p(max_score, p, max_seq_len) : window_width(max_score, p.oe - p.e, p.e, max_seq_len);
   if (ef) {
     const long long m = max_seq_len;
     const long long free_sum = std::min<long long>(p.span_pbf, m) + std::min<long long>(p.span_pef, m) + std::min<long long>(p.span_tbf, m) + std::min<long long>(p.span_tef, m);
@@ -591,7 +610,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   // Short wavefronts, score only (tier 5, short_kernel.hip): when the diagonal window of the budget fits 16 or 32 lanes, four or two
   // alignments share a wavefront and the rings live in registers (BASELINE configs[1]: 150 bp reads, budgets of ~14 once
   // they are tuned).  Pairs whose own window is wider (large |tlen - plen|) come back as BAND failures and go on as always.
-  if (!ef && !raw && !(p.ascii && !c->short_ascii_ok) && c->tuning.min_tier == 0 && !(bt && c->tuning.no_short_cigar) && wfa_short_supported(p.x, p.oe, p.e) && width + 1 <= 32 && max_score <= 30000) {
+  if (!ef && !tp2 && !raw && !(p.ascii && !c->short_ascii_ok) && c->tuning.min_tier == 0 && !(bt && c->tuning.no_short_cigar) && wfa_short_supported(p.x, p.oe, p.e) && width + 1 <= 32 && max_score <= 30000) {
     const int lanes = width + 1 <= 16 ? 16 : 32;
     p.rs = 0;
     const size_t lds = wfa_short_lds_bytes(p, lanes, bt);
@@ -619,13 +638,13 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     if (t == 0 && (width > 1024 || p.dm > 64)) continue;
     if (t == 1 && width > 8192) continue;
     if (t == 1 && few_pairs && width >= 1024 && !min_tier && wfa_align_lds_bytes(p, 2) <= budget[2]) continue;
-    int nb = ef ? wfa_align_ef_max_blocks_per_cu(t, bt, raw, lds) : wfa_align_max_blocks_per_cu(t, bt, raw, false, lds);
+    int nb = tp2 ? wfa_align_2p_max_blocks_per_cu(t, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(t, bt, raw, lds) : wfa_align_max_blocks_per_cu(t, bt, raw, false, lds);
     if (nb < 1) continue;
     // Occupancy-matched instantiation of the one-wave kernels: LDS decides how many rings a CU holds; compiled for 8 waves
     // per SIMD the kernel lives on 64 VGPRs and 78 SGPRs (123 scalar spills + scratch), which only pays when 8 waves per
     // SIMD really are resident.  The smallest of 4 / 6 / 7 / 8 that keeps all the rings LDS allows but at most one.
     int wpe = 8;
-    if (t == 0 && !raw && !ef) {
+    if (t == 0 && !raw && !ef && !tp2) {
       const int forced = c->tuning.waves_per_simd;
       for (int w : {4, 6, 7, 8}) if (4 * w >= nb - 1) { wpe = w; break; }
       // (gap extensions > 1: the general lean loop carries more scalar state than the e == 1 loop; compiled for 8 waves per SIMD -- 64
@@ -643,7 +662,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     // (profiles/r02/mid_lengths.txt).  tuning.t0_min_blocks: A/B.
     const int t0_min_blocks = c->tuning.t0_min_blocks > 0 ? c->tuning.t0_min_blocks : 10;
     if (t == 0 && !min_tier && nb < t0_min_blocks && width >= 384) continue;
-    if (t == 1 && !raw && !ef && c->tuning.exact_two_waves) {
+    if (t == 1 && !raw && !ef && !tp2 && c->tuning.exact_two_waves) {
       // A/B hook: TWO waves per alignment where four would run (same ring, same LDS; half the per-score bookkeeping per chunk, half the waves)
       const size_t lds2 = wfa_align_lds_bytes(p, 6);
       const int nb2 = wfa_align_max_blocks_per_cu(6, bt, raw, false, lds2);
@@ -653,7 +672,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     return true;
   }
   // hybrid ring: everything but the D rows in LDS (one workgroup of 16 waves per CU)
-  if (i16_ok && !raw && !ef && min_tier != 3) {
+  if (i16_ok && !raw && !ef && !tp2 && min_tier != 3) {
     const size_t lds_h = wfa_align_lds_bytes(p, 4);
     if (lds_h <= c->lds_per_block_max) {
       const int nb = wfa_align_max_blocks_per_cu(4, bt, raw, false, lds_h);
@@ -663,7 +682,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   p.rs = rs_plain;
   const size_t lds = wfa_align_lds_bytes(p, 3);
   if (lds > c->lds_per_block_max) return false;   // sequences themselves do not fit LDS
-  const int nb = ef ? wfa_align_ef_max_blocks_per_cu(3, bt, raw, lds) : wfa_align_max_blocks_per_cu(3, bt, raw, false, lds);
+  const int nb = tp2 ? wfa_align_2p_max_blocks_per_cu(3, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(3, bt, raw, lds) : wfa_align_max_blocks_per_cu(3, bt, raw, false, lds);
   *out = {3, width, max_score, lds, std::max(1, std::min(nb, 2))};
   return true;
 }
@@ -689,14 +708,28 @@ int zero_counter(wfagpu_amd_ctx* c, int idx, int count = 1) {
 }  // namespace
 
 // span == nullptr: end to end.  Else the ends-free kernels (align_kernel_ef.hip), exact search; d_ends: see the header.
+// pen2 != nullptr: two-piece gap-affine (align_kernel_2p.hip), exact search, end to end; `pen` is ignored.
 static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
                              affine_penalties_t pen, int max_error, int band, int band_width,
                              bool compute_cigar, int32_t* d_scores,
                              const char** d_text, const unsigned long long** d_off,
-                             const unsigned int** d_len, const wfagpu_amd_span_t* span, int32_t* d_ends) {
+                             const unsigned int** d_len, const wfagpu_amd_span_t* span, int32_t* d_ends,
+                             const wfagpu_amd_penalties2p_t* pen2 = nullptr) {
   if (!c || !b || !d_scores) return -1;
   const bool ef = span != nullptr;
-  if (ef) { band = -1; band_width = 0; }      // (exact search: a band is a permission to approximate, not an obligation)
+  const bool tp2 = pen2 != nullptr;
+  if (ef || tp2) { band = -1; band_width = 0; }      // (exact search: a band is a permission to approximate, not an obligation)
+  if (tp2 && ef) { fprintf(stderr, "[!] ERROR: two-piece penalties are not combined with an ends-free span\n"); return -1; }
+  int o2 = 0, e2 = 0;      // the second piece (pen holds x and the first)
+  if (tp2) {
+    // (WFA2 rejects anything else: wavefront_penalties_set_affine2p)
+    if (pen2->mismatch <= 0 || pen2->gap_opening1 <= 0 || pen2->gap_extension1 <= 0 || pen2->gap_opening2 <= 0 || pen2->gap_extension2 <= 0) {
+      fprintf(stderr, "[!] ERROR: two-piece penalties must all be positive (got %d,%d,%d,%d,%d)\n", pen2->mismatch, pen2->gap_opening1, pen2->gap_extension1,
+              pen2->gap_opening2, pen2->gap_extension2);
+      return -1;
+    }
+    pen.x = pen2->mismatch; pen.o = pen2->gap_opening1; pen.e = pen2->gap_extension1; o2 = pen2->gap_opening2; e2 = pen2->gap_extension2;
+  }
   if (ef && (span->pattern_begin_free < 0 || span->pattern_end_free < 0 || span->text_begin_free < 0 || span->text_end_free < 0)) {
     fprintf(stderr, "[!] ERROR: the members of a span must not be negative (got %d,%d,%d,%d)\n", span->pattern_begin_free, span->pattern_end_free,
             span->text_begin_free, span->text_end_free);
@@ -713,9 +746,9 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
   int pen_scale = 1;
   {
     auto gcd = [](int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; };
-    const int g = gcd(gcd(pen.x, pen.o), pen.e);
+    const int g = gcd(gcd(gcd(pen.x, pen.o), pen.e), gcd(o2, e2));      // (gcd(a, 0) = a: gap-affine as before)
     if (g > 1) {
-      pen_scale = g; pen.x /= g; pen.o /= g; pen.e /= g; max_error = std::max(1, max_error / g);
+      pen_scale = g; pen.x /= g; pen.o /= g; pen.e /= g; o2 /= g; e2 /= g; max_error = std::max(1, max_error / g);
       if (want_band) band = std::max(1, band / g);     // (the re-centring period counts scores)
     }
   }
@@ -779,6 +812,9 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
   ap.x = pen.x; ap.oe = oe; ap.e = pen.e;
   ap.dm = std::max(pen.x, oe) + 1;
   ap.de = pen.e + 1;
+  if (tp2) { ap.oe2 = o2 + e2; ap.e2 = e2; ap.de2 = e2 + 1; ap.dm = std::max(ap.dm, ap.oe2 + 1); }
+  // every operation of an alignment costs at least this much (sizes the op lists and texts of the backtrace)
+  const int min_op_cost = tp2 ? std::min(pen.x, std::min(pen.e, e2)) : std::min(pen.x, pen.e);
   { int bk = 64; while (bk < ap.dm) bk <<= 1; ap.book_mask = bk - 1; }
   ap.seq_words_cap = (int)((max_len + 15) / 16 + 1);
   ap.score = d_scores;
@@ -803,7 +839,13 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
     if (w > 1024) return 0.0;      // (wider wavefronts run on the multi-wave tiers: rows behind a row table)
     return 64.0 * (double)((w + 15) / 16) * (double)(B / 4 + 1) + 512.0;
   };
-  est_pair_bytes = std::max(est_pair_bytes, tiled_pair_bytes(std::min<long long>(max_error, 2ll * batch_max_len * std::max(pen.x, pen.e))));
+  if (!tp2) est_pair_bytes = std::max(est_pair_bytes, tiled_pair_bytes(std::min<long long>(max_error, 2ll * batch_max_len * std::max(pen.x, pen.e))));
+  else {
+    // (two pieces: one byte per cell of the two-piece diamond -- rows behind a row table in every tier.  The wavefront gains a diagonal on
+    // each side every min(e1, e2) scores and the reach takes them back at the same rate: B^2 / (2 min(e1, e2)) cells under a budget B)
+    const double B = std::min<unsigned>(max_error, 2 * max_len);
+    est_pair_bytes = 0.5 * (B + 1) * (B + 1) / std::min(pen.e, e2) + 16.0 * B + 4096.0;
+  }
   if (ef) {
     // (ends-free: every score's row starts as wide as the free begins and only grows: rows behind a row table in every tier)
     const double m = batch_max_len;
@@ -843,7 +885,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
   // 18 us + the gap between two launches of a 168 us step of 100k configs[1] pairs.  (ASCII dword indices are 32-bit there.)
   // (sequences_bytes may be missing from a caller's batch record: four times the packed words bound the ASCII layout from above)
   c->short_ascii_ok = std::max<size_t>(b->sequences_bytes, b->packed_bytes * 4) < ((size_t)1 << 34);
-  const bool short_fuses = !ef && wfa_short_supported(pen.x, oe, pen.e) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
+  const bool short_fuses = !ef && !tp2 && wfa_short_supported(pen.x, oe, pen.e) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
   const bool fused_pack = !prepacked && (b->max_seq_len >= 512u || short_fuses) && !c->tuning.no_fused_pack;
   // Every status starts as PENDING = 0: written by the pack kernel where it runs (it visits every pair anyway), by a memset (a
   // launch of its own, ~5 us + a gap) where it does not -- queued by whoever reads the array first (ensure_status), and not at all
@@ -997,7 +1039,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
         if (tp.tier == 3 || tp.tier == 4) {
           ap.ring16 = max_len <= 32766u ? 1 : 0;
           const size_t stride = tp.tier == 4 ? ((((size_t)ap.de * ap.rs * 2) + 255) & ~(size_t)255)     // hybrid: the D ring only
-                                             : ((((size_t)(ap.dm + 2 * ap.de) * ap.rs * (ap.ring16 ? 2 : 4)) + 255) & ~(size_t)255);
+                                             : ((((size_t)(ap.dm + 2 * ap.de + 2 * ap.de2) * ap.rs * (ap.ring16 ? 2 : 4)) + 255) & ~(size_t)255);
           const int g = (int)std::min<uint32_t>(n_cur, (uint32_t)(c->num_cus * tp.blocks_per_cu));
           if (c->gring.ensure(stride * g, st)) return -1;
           ap.gring = c->gring.p; ap.gring_stride = stride;
@@ -1098,6 +1140,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
           if (cigar_now && !ap.arena_top_known) LAUNCH_K(k_bump, dim3(1), dim3(64), 0, st, ap.arena_top, (unsigned long long)n_cur * wfa_short_bt_slot_units(ap.max_score, tp.wpe), ap.arena_units);
         }
         else if (ef) wfa_launch_align_ef(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
+        else if (tp2) wfa_launch_align_2p(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else wfa_launch_align(ap, tp.tier, cigar_now, raw, grid, st, tp.wpe, L.e0, L.e1);
         {
           const hipError_t le = hipGetLastError();
@@ -1150,15 +1193,15 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
       } else if (fused_tail)
         LAUNCH_K_END(k_chain_tail, dim3(std::min<uint32_t>(std::max(cdiv(n_chain, 2048), cdiv(n, 8192)), 256u)), dim3(256), 0, st, ev_tail, (const uint32_t*)chain_list, n_chain,
                                static_cast<const uint32_t*>(c->status.p), MASK(WFA_ST_BAND) | MASK(WFA_ST_SCORE), tail_out, tail_count, ap.work_counter,
-                               (const int32_t*)d_scores, static_cast<const uint32_t*>(c->cells.p), std::min(pen.x, pen.e), item_chars, ct, n,
+                               (const int32_t*)d_scores, static_cast<const uint32_t*>(c->cells.p), min_op_cost, item_chars, ct, n,
                                (const unsigned long long*)ap.wave_parts, parts_n, tail_parts_out);
       else
         LAUNCH_K_END(k_trace_bounds, dim3(std::min<uint32_t>(std::max(cdiv(n_chain, 2048), cdiv(n, 8192)), 256u)), dim3(256), 0, st, ev_tail, (const uint32_t*)chain_list, n_chain,
                                static_cast<const uint32_t*>(c->status.p), (const int32_t*)d_scores,
-                               static_cast<const uint32_t*>(c->cells.p), std::min(pen.x, pen.e), item_chars, ct, n);
+                               static_cast<const uint32_t*>(c->cells.p), min_op_cost, item_chars, ct, n);
       if (cigar_now) {
         // which kernels walk and replay (trace_layout.h: two steps, the largest score of the pass arrives with the counters)
-        const TracePlanIn plan_in{c->lds_per_block_max, c->tuning.trace_mode, c->tuning.emit_pairs, raw, max_len, n_chain, s_hi, std::min(pen.x, pen.e), item_chars, extra_items};
+        const TracePlanIn plan_in{c->lds_per_block_max, c->tuning.trace_mode, c->tuning.emit_pairs, raw, max_len, n_chain, s_hi, min_op_cost, item_chars, extra_items};
         TracePlan plan = trace_plan_begin(plan_in);
         unsigned long long ops_need, text_sum;
         if (plan.by_bound) { ops_need = plan.ops_bound + 256; text_sum = plan.text_bound; }
@@ -1166,7 +1209,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
           // (a chain without a tail kernel: nobody has formed the sums yet.  Cells and the unfinished count stay with the launch's
           // partial sums)
           if (solo) LAUNCH_K(k_trace_bounds, dim3(std::min<uint32_t>(std::max(cdiv(n_chain, 2048), 1u), 256u)), dim3(256), 0, st, (const uint32_t*)chain_list, n_chain,
-                             static_cast<const uint32_t*>(c->status.p), (const int32_t*)d_scores, static_cast<const uint32_t*>(nullptr), std::min(pen.x, pen.e), item_chars, ct, 0u);
+                             static_cast<const uint32_t*>(c->status.p), (const int32_t*)d_scores, static_cast<const uint32_t*>(nullptr), min_op_cost, item_chars, ct, 0u);
           if (read_counters(c)) return -1;
           ops_need = c->h_counters[CT_SUM_OPS] + 256; text_sum = c->h_counters[CT_SUM_TEXT];
         }
@@ -1189,12 +1232,13 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
         tp.ops_lds_bytes = plan.ops_lds_bytes; tp.text_lds_bytes = plan.text_lds_bytes;
         tp.packed = ap.packed; tp.meta = ap.meta; tp.work = chain_list; tp.n_work = n_chain;
         tp.x = pen.x; tp.oe = oe; tp.e = pen.e;
+        tp.oe2 = ap.oe2; tp.e2 = ap.e2;
         tp.score = d_scores; tp.status = static_cast<const uint32_t*>(c->status.p);
         tp.score_fix = (want_band && !raw) ? d_scores : nullptr;
         tp.arena = ap.arena; tp.arena_bytes = (unsigned long long)c->arena.cap; tp.bt_final_row = ap.bt_final_row;
         tp.ops = static_cast<uint8_t*>(c->ops.p); tp.ops_cap = c->ops.cap; tp.ops_top = ct + CT_OPS;
         tp.text = static_cast<char*>(c->text[c->out_set].p); tp.text_cap = c->text[c->out_set].cap; tp.text_top = ct + CT_TEXT;
-        tp.min_op_cost = std::min(pen.x, pen.e);
+        tp.min_op_cost = min_op_cost;
         tp.item_chars = item_chars;
         tp.extra_items = extra_items;
         if (ef) { tp.span_pbf = ap.span_pbf; tp.span_tbf = ap.span_tbf; tp.ends = d_ends; }
@@ -1207,7 +1251,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
         tp.cigar_len = static_cast<uint32_t*>(c->cig_len[c->out_set].p);
         // (ev_t0 / ev_t1: start of the first and end of the last backtrace kernel)
         tp.walk_grid_cap = 2 * c->num_cus;      // (two workgroups = eight wavefronts per CU: trace_kernel.hip, wfa_walk_kernel)
-        traced = wfa_launch_trace(tp, st, c->ev_t0, c->ev_t1);
+        traced = tp2 ? wfa_launch_trace_2p(tp, st, c->ev_t0, c->ev_t1) : wfa_launch_trace(tp, st, c->ev_t0, c->ev_t1);
         HIP_TRY(hipGetLastError());
         // ---- pairs that ran out of arena go into the next pass (CIGAR calls only: score-only calls have no arena) ----
         // (none can where a tier-5 launch was the chain's only one and its slots fit the arena: the backtrace kernel is the chain's last
@@ -1344,7 +1388,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
       // (tuned budgets pay where they narrow a wide window -- or, score-only, where they bring it down to what the
       // several-alignments-per-wavefront tier holds)
       const bool short_ok = wfa_short_supported(pen.x, oe, pen.e) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar);
-      const bool would_tune = !ef && n >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) && (w_me > 128 || (w_me > 15 && short_ok));
+      const bool would_tune = !ef && !tp2 && n >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) && (w_me > 128 || (w_me > 15 && short_ok));
       bool inherited = false;
       if (would_tune && c->same_stream)
         for (int i = 0; i < c->n_saved_q; ++i) {
@@ -1390,7 +1434,8 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
       const bool short_ok2 = wfa_short_supported(pen.x, oe, pen.e) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar);
       // (the budgets decide whether the band is worth using and serve the exact kernels; with the band forced neither applies)
       // (ends-free: no budgets from a sample -- the careful loop is the only one, and a read's score says little about a window's)
-      const bool try_budget = !ef && !raw && n_pending >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) &&
+      // (two pieces: none either -- switched off, not tuned: DESIGN.md section 4.7)
+      const bool try_budget = !ef && !tp2 && !raw && n_pending >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) &&
                               (w_me2 > 128 || (w_me2 > 15 && short_ok2));
       int saved_idx = -1;
       if (try_budget && c->same_stream) {
@@ -1555,7 +1600,20 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
     const wfagpu_amd_span_t span{ls[0], ls[1], ls[2], ls[3]};
     return align_device_impl(c, b, pen, max_error, band, band_width, compute_cigar, d_scores, d_text, d_off, d_len, &span, nullptr);
   }
+  // (the same for configured two-piece penalties: wfagpu_amd_configure_affine2p)
+  const int* const l2 = wfa_lane_affine2p5();
+  if (l2) {
+    const wfagpu_amd_penalties2p_t p2{l2[0], l2[1], l2[2], l2[3], l2[4]};
+    return align_device_impl(c, b, pen, max_error, band, band_width, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, &p2);
+  }
   return align_device_impl(c, b, pen, max_error, band, band_width, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr);
+}
+
+extern "C" int wfagpu_amd_align_device_2p(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b, const wfagpu_amd_penalties2p_t* pens, int max_error,
+                                          bool compute_cigar, int32_t* d_scores, const char** d_text, const unsigned long long** d_off,
+                                          const unsigned int** d_len) {
+  if (!pens) { fprintf(stderr, "[!] ERROR: wfagpu_amd_align_device_2p needs penalties\n"); return -1; }
+  return align_device_impl(c, b, affine_penalties_t{}, max_error, -1, 0, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, pens);
 }
 
 extern "C" int wfagpu_amd_align_device_span(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b, affine_penalties_t pen, int max_error,

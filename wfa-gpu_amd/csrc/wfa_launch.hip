@@ -51,6 +51,11 @@ std::mutex g_span_mutex;
 bool g_span_set = false;
 int g_span[4] = {0, 0, 0, 0};
 thread_local const int* t_lane_span = nullptr;
+// The process-wide two-piece penalties (wfagpu_amd_configure_affine2p), kept and handed over the same way (wfa_lane_affine2p5);
+// under the span's mutex: the two are never configured together.
+bool g_2p_set = false;
+int g_2p[5] = {0, 0, 0, 0, 0};
+thread_local const int* t_lane_2p = nullptr;
 }  // namespace
 
 bool wfa_configured_span(int* out4) {
@@ -59,6 +64,28 @@ bool wfa_configured_span(int* out4) {
   return g_span_set;
 }
 const int* wfa_lane_span4() { return t_lane_span; }
+bool wfa_configured_affine2p(int* out5) {
+  std::lock_guard<std::mutex> lock(g_span_mutex);
+  if (out5 && g_2p_set) for (int i = 0; i < 5; ++i) out5[i] = g_2p[i];
+  return g_2p_set;
+}
+const int* wfa_lane_affine2p5() { return t_lane_2p; }
+
+extern "C" int wfagpu_amd_configure_affine2p(const wfagpu_amd_penalties2p_t* pens) {
+  if (pens && (pens->mismatch <= 0 || pens->gap_opening1 <= 0 || pens->gap_extension1 <= 0 || pens->gap_opening2 <= 0 || pens->gap_extension2 <= 0)) {
+    fprintf(stderr, "[!] ERROR: two-piece penalties must all be positive (got %d,%d,%d,%d,%d)\n", pens->mismatch, pens->gap_opening1, pens->gap_extension1,
+            pens->gap_opening2, pens->gap_extension2);
+    return -1;
+  }
+  std::lock_guard<std::mutex> lock(g_span_mutex);
+  if (pens && g_span_set) {
+    fprintf(stderr, "[!] ERROR: two-piece penalties are not combined with an ends-free span (one is configured)\n");
+    return -1;
+  }
+  g_2p_set = pens != nullptr;
+  if (pens) { g_2p[0] = pens->mismatch; g_2p[1] = pens->gap_opening1; g_2p[2] = pens->gap_extension1; g_2p[3] = pens->gap_opening2; g_2p[4] = pens->gap_extension2; }
+  return 0;
+}
 
 extern "C" int wfagpu_amd_configure_span(const wfagpu_amd_span_t* span) {
   if (span && (span->pattern_begin_free < 0 || span->pattern_end_free < 0 || span->text_begin_free < 0 || span->text_end_free < 0)) {
@@ -67,6 +94,10 @@ extern "C" int wfagpu_amd_configure_span(const wfagpu_amd_span_t* span) {
     return -1;
   }
   std::lock_guard<std::mutex> lock(g_span_mutex);
+  if (span && g_2p_set) {
+    fprintf(stderr, "[!] ERROR: an ends-free span is not combined with two-piece penalties (they are configured)\n");
+    return -1;
+  }
   g_span_set = span != nullptr;
   if (span) { g_span[0] = span->pattern_begin_free; g_span[1] = span->pattern_end_free; g_span[2] = span->text_begin_free; g_span[3] = span->text_end_free; }
   return 0;
@@ -199,6 +230,9 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
   // the program with free borders -- utils/verification.h)
   int sp4[4] = {0, 0, 0, 0};
   const int* const span = wfa_configured_span(sp4) ? sp4 : nullptr;
+  // (under configured two-piece penalties: a gap run priced by the cheaper piece, the score checked against the five-table program)
+  int q5[5] = {0, 0, 0, 0, 0};
+  const int* const p2 = wfa_configured_affine2p(q5) ? q5 : nullptr;
   auto worker = [&](unsigned) {
     verification_scratch_t scratch = {nullptr, 0};     // this worker's, for all its pairs; freed below
     for (;;) {
@@ -214,14 +248,16 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
         if (a.cigar) {
           const char* cg = a.results[i].cigar.buffer;
           const bool c1 = check_cigar_edit(text, pattern, m.text_len, m.pattern_len, cg);
-          const bool c2 = span ? check_affine_distance_span(text, pattern, m.text_len, m.pattern_len, dist, a.opt.penalties.x,
+          const bool c2 = p2 ? check_affine2p_distance(text, pattern, m.text_len, m.pattern_len, dist, p2[0], p2[1], p2[2], p2[3], p2[4], cg)
+                        : span ? check_affine_distance_span(text, pattern, m.text_len, m.pattern_len, dist, a.opt.penalties.x,
                                                             a.opt.penalties.o, a.opt.penalties.e, cg, span)
                                : check_affine_distance(text, pattern, m.text_len, m.pattern_len, dist, a.opt.penalties.x,
                                                        a.opt.penalties.o, a.opt.penalties.e, cg);
           if (!c1) LOG_ERROR("Incorrect cigar (%ld). Distance: %d. CIGAR: %s", i, dist, cg);
           ok = c1 && c2;
         }
-        const int cpu = span ? verification_cpu_score_span_scratch(pattern, text, m.pattern_len, m.text_len, a.opt.penalties.x,
+        const int cpu = p2 ? verification_cpu_score_2p_scratch(pattern, text, m.pattern_len, m.text_len, p2[0], p2[1], p2[2], p2[3], p2[4], &scratch)
+                      : span ? verification_cpu_score_span_scratch(pattern, text, m.pattern_len, m.text_len, a.opt.penalties.x,
                                                                    a.opt.penalties.o, a.opt.penalties.e, span, &scratch)
                              : verification_cpu_score_scratch(pattern, text, m.pattern_len, m.text_len, a.opt.penalties.x,
                                                               a.opt.penalties.o, a.opt.penalties.e, &scratch);
@@ -915,9 +951,23 @@ int run_device(const CallArgs& a, Shard& sh) {
         if (!warned.exchange(true)) fprintf(stderr, "[!] WARNING: the adaptive band is not combined with an ends-free span: running the exact search\n");
       }
       t_lane_span = under_span ? sp4 : nullptr;
+      // (the same for configured two-piece penalties -- wfagpu_amd_configure_affine2p --: the penalties of the options are ignored,
+      // a band is not used; each said once)
+      int q5[5];
+      const bool under_2p = wfa_configured_affine2p(q5);
+      if (under_2p) {
+        static std::atomic<bool> said{false};
+        if (!said.exchange(true)) fprintf(stderr, "[!] NOTE: two-piece penalties %d,%d,%d,%d,%d are configured: the gap-affine penalties of the call are ignored\n", q5[0], q5[1], q5[2], q5[3], q5[4]);
+        if (a.opt.band > 0 && a.opt.threads_per_block > 0) {
+          static std::atomic<bool> warned2{false};
+          if (!warned2.exchange(true)) fprintf(stderr, "[!] WARNING: the adaptive band is not combined with two-piece penalties: running the exact search\n");
+        }
+      }
+      t_lane_2p = under_2p ? q5 : nullptr;
       const int arc = wfagpu_amd_align_device(L.ctx, &wb, a.opt.penalties, a.opt.max_error, a.opt.band, a.opt.threads_per_block, a.cigar,
                                               d_sc, &bo.d_text, &bo.d_off, &bo.d_len);
       t_lane_span = nullptr;
+      t_lane_2p = nullptr;
       if (arc) return arc;
       bo.d_scores = d_sc;
       if (a.cigar) { wfagpu_amd_stats_t stt; wfagpu_amd_last_stats(L.ctx, &stt); bo.text_bytes = stt.text_bytes; }

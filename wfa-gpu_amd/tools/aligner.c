@@ -59,6 +59,8 @@ static void usage(const char* prog) {
            "\t-c, --check                       Verify results against a CPU computation\n"
            "\t    --ends-free <pb,pe,tb,te>     Ends-free alignment: bases that may stay unaligned at no cost at the pattern's\n"
            "\t                                  begin / end and the text's begin / end (exact search: not with -B)\n"
+           "\t    --affine2p <x,o1,e1,o2,e2>    Two-piece gap-affine penalties: a gap of n bases costs min(o1+n*e1, o2+n*e2)\n"
+           "\t                                  (WFA2's defaults: 4,6,2,24,1; exact search: not with -g, -B or --ends-free)\n"
            "[System]\n"
            "\t-t, --threads-per-block <int>     Accepted for compatibility (band width in banded mode)\n"
            "\t-w, --workers <int>               Accepted for compatibility\n"
@@ -81,11 +83,12 @@ int main(int argc, char** argv) {
         {"batch-size", required_argument, 0, 'b'}, {"band", required_argument, 0, 'B'},
         {"check", no_argument, 0, 'c'}, {"threads-per-block", required_argument, 0, 't'},
         {"workers", required_argument, 0, 'w'}, {"help", no_argument, 0, 'h'}, {"stage-times", no_argument, 0, 1000},
-        {"ends-free", required_argument, 0, 1001}, {0, 0, 0, 0}};
+        {"ends-free", required_argument, 0, 1001}, {"affine2p", required_argument, 0, 1002}, {0, 0, 0, 0}};
     const char *seq_path = NULL, *q_path = NULL, *t_path = NULL, *out_path = NULL, *pen_str = NULL;
     long n_read = 0, max_distance = -1, batch_size = -1, band_arg = -2, tpb = -1, workers = -1;
     bool print_out = false, verbose = false, cigar = false, check = false, stage_times = false;
     const char* span_str = NULL;
+    const char* pen2_str = NULL;
 
 
     int c;
@@ -109,6 +112,7 @@ int main(int argc, char** argv) {
             case 'w': workers = atol(optarg); break;
             case 1000: stage_times = true; break;      /* (not in the reference: the library's stage clocks of the call on stderr) */
             case 1001: span_str = optarg; break;       /* (not in the reference: WFA2's ends-free alignment) */
+            case 1002: pen2_str = optarg; break;       /* (not in the reference: WFA2's gap_affine_2p) */
             case 'h': usage(argv[0]); exit(0);
             default: break;      /* an option the tool does not know is skipped, like the reference's parser does (utils/arg_handler.c:97-140) */
         }
@@ -139,7 +143,28 @@ int main(int argc, char** argv) {
         LOG_INFO("Ends-free alignment: pattern begin/end free %d/%d, text begin/end free %d/%d.", span.pattern_begin_free, span.pattern_end_free,
                  span.text_begin_free, span.text_end_free)
     }
+    /* --affine2p: five positive integers, nothing behind them; not together with -g, -B or --ends-free.  Checked before any device
+     * work, like --ends-free. */
+    wfagpu_amd_penalties2p_t pen2 = {0, 0, 0, 0, 0};
+    if (pen2_str) {
+        char tail = 0;
+        if (sscanf(pen2_str, "%d,%d,%d,%d,%d%c", &pen2.mismatch, &pen2.gap_opening1, &pen2.gap_extension1, &pen2.gap_opening2, &pen2.gap_extension2, &tail) != 5 ||
+            pen2.mismatch <= 0 || pen2.gap_opening1 <= 0 || pen2.gap_extension1 <= 0 || pen2.gap_opening2 <= 0 || pen2.gap_extension2 <= 0) {
+            LOG_ERROR("--affine2p takes five positive integers x,o1,e1,o2,e2 (got \"%s\").", pen2_str)
+            usage(argv[0]);
+            return 1;
+        }
+        if (pen_str || band_arg != -2 || span_str) {
+            LOG_ERROR("--affine2p is an exact end-to-end search under its own penalties: it is not combined with -g, -B or --ends-free.")
+            usage(argv[0]);
+            return 1;
+        }
+        if (wfagpu_amd_configure_affine2p(&pen2) != 0) return 1;
+        LOG_INFO("Two-piece gap-affine penalties: M=0, X=%d, O1=%d, E1=%d, O2=%d, E2=%d.", pen2.mismatch, pen2.gap_opening1, pen2.gap_extension1,
+                 pen2.gap_opening2, pen2.gap_extension2)
+    }
     int x = 2, o = 3, e = 1;
+    if (pen2_str) { x = pen2.mismatch; o = pen2.gap_opening1; e = pen2.gap_extension1; }      /* (sizes the default -e below; the library ignores them) */
     if (pen_str && sscanf(pen_str, "%d,%d,%d", &x, &o, &e) != 3) {
         LOG_WARN("Invalid penalties format provided. Using default penalties (0,2,3,1).")
         x = 2; o = 3; e = 1;

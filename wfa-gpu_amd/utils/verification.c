@@ -260,3 +260,113 @@ int verification_cpu_score_span_scratch(const char* pattern, const char* text, s
     }
     return s;
 }
+
+/* ---- two-piece gap-affine (see verification.h) ---- */
+static long gap2p_cost(long n, int o1, int e1, int o2, int e2) {
+    const long a = o1 + n * e1, b = o2 + n * e2;
+    return a < b ? a : b;
+}
+
+bool check_affine2p_distance(const char* text, const char* pattern, size_t tlen, size_t plen,
+                             int distance, int x, int o1, int e1, int o2, int e2, const char* cigar) {
+    (void)text; (void)pattern; (void)tlen; (void)plen;
+    long cost = 0, gap = 0;     /* gap: bases of the I / D run that is open */
+    char prev = 0;
+    const char* c = cigar;
+    while (*c) {
+        long n; char op;
+        c = next_item(c, &n, &op);
+        if (!c) return false;
+        if (op != 'M' && op != 'X' && op != 'I' && op != 'D') return false;
+        /* a run ends where the operation changes: priced as a whole, by the cheaper piece */
+        if (op != prev && gap) { cost += gap2p_cost(gap, o1, e1, o2, e2); gap = 0; }
+        if (op == 'X') cost += n * x;
+        else if (op == 'I' || op == 'D') gap += n;
+        prev = op;
+    }
+    if (gap) cost += gap2p_cost(gap, o1, e1, o2, e2);
+    return cost == distance;
+}
+
+int verification_cpu_score_2p(const char* pattern, const char* text, size_t plen, size_t tlen, int x, int o1, int e1, int o2, int e2) {
+    verification_scratch_t sc = {NULL, 0};
+    const int s = verification_cpu_score_2p_scratch(pattern, text, plen, tlen, x, o1, e1, o2, e2, &sc);
+    verification_scratch_free(&sc);
+    return s;
+}
+
+/* The program of verification_cpu_score_scratch with five score-indexed tables: M, and I / D once per piece. */
+int verification_cpu_score_2p_scratch(const char* pattern, const char* text, size_t plen_, size_t tlen_,
+                                      int x, int o1, int e1, int o2, int e2, verification_scratch_t* sc) {
+    const int plen = (int)plen_, tlen = (int)tlen_;
+    const int W = plen + tlen + 5, K0 = plen + 2;
+    const int NONE = -(1 << 28);
+    const int oe[2] = {o1 + e1, o2 + e2}, ex[2] = {e1, e2};
+    int depth = x;
+    if (oe[0] > depth) depth = oe[0];
+    if (oe[1] > depth) depth = oe[1];
+    ++depth;
+    const size_t need = (size_t)W * 5 * (size_t)depth;
+    if (!sc) return -1;
+    if (need > sc->cap) {
+        free(sc->buf);
+        sc->cap = need + need / 4;
+        sc->buf = (int*)malloc(sizeof(int) * sc->cap);
+        if (!sc->buf) { sc->cap = 0; return -1; }
+    }
+    int* T[5];      /* M, I1, D1, I2, D2 */
+    for (int t = 0; t < 5; ++t) T[t] = sc->buf + (size_t)t * W * depth;
+    const int kend = tlen - plen;
+    for (int t = 0; t < 5; ++t)
+        for (int r = 0; r < depth; ++r)
+            for (int k = -1; k <= 1; ++k) T[t][(size_t)r * W + K0 + k] = NONE;
+    {
+        int h = 0;
+        while (h < plen && h < tlen && pattern[h] == text[h]) ++h;
+        T[0][K0] = h;
+        if (kend == 0 && h >= tlen) return 0;
+    }
+    int lo = 0, hi = 0;
+    int s;
+    for (s = 1;; ++s) {
+        const size_t row = (size_t)(s % depth) * W;
+        const int* Mx = s >= x ? T[0] + (size_t)((s - x) % depth) * W : NULL;
+        if (lo > -plen) {
+            --lo;
+            for (int t = 0; t < 5; ++t) for (int r = 0; r < depth; ++r) T[t][(size_t)r * W + K0 + lo - 1] = NONE;
+        }
+        if (hi < tlen) {
+            ++hi;
+            for (int t = 0; t < 5; ++t) for (int r = 0; r < depth; ++r) T[t][(size_t)r * W + K0 + hi + 1] = NONE;
+        }
+        for (int k = lo; k <= hi; ++k) {
+            int m = NONE;
+            if (Mx && Mx[K0 + k] >= 0) m = Mx[K0 + k] + 1;
+            if (m >= 0 && (m > tlen || m - k > plen)) m = NONE;
+            for (int pc = 0; pc < 2; ++pc) {
+                const int* Mo = s >= oe[pc] ? T[0] + (size_t)((s - oe[pc]) % depth) * W : NULL;
+                const int* Ie = s >= ex[pc] ? T[1 + 2 * pc] + (size_t)((s - ex[pc]) % depth) * W : NULL;
+                const int* De = s >= ex[pc] ? T[2 + 2 * pc] + (size_t)((s - ex[pc]) % depth) * W : NULL;
+                int ins = NONE, del = NONE;
+                if (Mo && Mo[K0 + k - 1] > ins) ins = Mo[K0 + k - 1];
+                if (Ie && Ie[K0 + k - 1] > ins) ins = Ie[K0 + k - 1];
+                if (ins >= 0) ++ins;
+                if (Mo && Mo[K0 + k + 1] > del) del = Mo[K0 + k + 1];
+                if (De && De[K0 + k + 1] > del) del = De[K0 + k + 1];
+                if (ins >= 0 && (ins > tlen || ins - k > plen)) ins = NONE;
+                if (del >= 0 && (del > tlen || del - k > plen)) del = NONE;
+                T[1 + 2 * pc][row + K0 + k] = ins; T[2 + 2 * pc][row + K0 + k] = del;
+                if (ins > m) m = ins;
+                if (del > m) m = del;
+            }
+            if (m >= 0) {
+                int h = m, v = m - k;
+                while (v < plen && h < tlen && pattern[v] == text[h]) { ++v; ++h; }
+                m = h;
+            }
+            T[0][row + K0 + k] = m;
+        }
+        if (kend >= lo && kend <= hi && T[0][row + K0 + kend] >= tlen) break;
+    }
+    return s;
+}

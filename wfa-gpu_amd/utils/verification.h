@@ -49,6 +49,16 @@ int verification_cpu_score_span_scratch(const char* pattern, const char* text, s
 int verification_cpu_score_span(const char* pattern, const char* text, size_t plen, size_t tlen,
                                 int x, int o, int e, const int* span);
 
+/* Two-piece gap-affine (wfagpu_amd_penalties2p_t; include/wfa_gpu_device.h): a gap run of n bases is priced
+ * min(o1 + n e1, o2 + n e2) -- a CIGAR does not say which piece a gap used; the score is checked against the
+ * program of verification_cpu_score_scratch with five tables (M, and I / D once per piece). */
+bool check_affine2p_distance(const char* text, const char* pattern, size_t tlen, size_t plen,
+                             int distance, int x, int o1, int e1, int o2, int e2, const char* cigar);
+int verification_cpu_score_2p_scratch(const char* pattern, const char* text, size_t plen, size_t tlen,
+                                      int x, int o1, int e1, int o2, int e2, verification_scratch_t* scratch);
+int verification_cpu_score_2p(const char* pattern, const char* text, size_t plen, size_t tlen,
+                              int x, int o1, int e1, int o2, int e2);
+
 #ifdef __cplusplus
 }
 #endif
