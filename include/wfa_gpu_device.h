@@ -168,7 +168,7 @@ int wfagpu_amd_prime(wfagpu_amd_ctx_t* ctx);
 void wfagpu_amd_debug_times(const wfagpu_amd_ctx_t* ctx, const void** d_records, unsigned int* records, int* waves);
 /* Diagnostics: which of the code objects that only some callers load this process has entered so far (launched, queried or
  * primed a kernel of) -- bit 0: the ends-free wavefront kernels, bit 1: the two-piece wavefront kernels, bit 2: the two-piece
- * backtrace kernels.  Process-wide, never cleared.  A gap-affine end-to-end caller reads 0. */
+ * backtrace kernels, bit 3: the wf-adaptive wavefront kernels.  Process-wide, never cleared.  A gap-affine end-to-end caller reads 0. */
 unsigned int wfagpu_amd_debug_code_objects(void);
 
 /* The HIP stream (hipStream_t) the context runs on -- its own, or the one given at creation. */
@@ -253,6 +253,25 @@ int wfagpu_amd_align_device_2p(wfagpu_amd_ctx_t* ctx, const wfagpu_amd_batch_t* 
  * NULL: back to gap-affine.  A member <= 0, or a span is configured: rejected (-1, message), state unchanged -- as is a span
  * while two-piece penalties are configured. */
 int wfagpu_amd_configure_affine2p(const wfagpu_amd_penalties2p_t* penalties);
+
+/* WFA-Adaptive, WFA2's default heuristic (wavefront_aligner_set_heuristic_wfadaptive; its defaults: 10, 50, 1): every
+ * steps_between_cutoffs scores whose M wavefront holds at least min_wavefront_length diagonals, the diagonals at its ends whose
+ * distance to the end of the alignment exceeds the smallest one of the wavefront by more than max_distance_threshold are
+ * dropped.  The search always finishes; the score can lie above the optimum.  Scores and CIGARs are WFA2's under the same
+ * parameters.  End to end, gap-affine (no band, no span, no second piece). */
+typedef struct { int min_wavefront_length, max_distance_threshold, steps_between_cutoffs; } wfagpu_amd_wfadaptive_t;
+
+/* wfagpu_amd_align_device under the heuristic; max_error is the score budget as there (a pair whose heuristic score passes it is
+ * escalated like any other).  heuristic == NULL: wfagpu_amd_align_device with BAND_NONE.  min_wavefront_length < 1,
+ * max_distance_threshold < 0 or steps_between_cutoffs < 1: -1. */
+int wfagpu_amd_align_device_adaptive(wfagpu_amd_ctx_t* ctx, const wfagpu_amd_batch_t* batch, affine_penalties_t penalties, int max_error,
+                                     const wfagpu_amd_wfadaptive_t* heuristic, bool compute_cigar, int32_t* d_scores,
+                                     const char** d_text, const unsigned long long** d_off, const unsigned int** d_len);
+
+/* Process-wide, like wfagpu_amd_configure_span: launch_alignments*, wfagpu_align and the CLI align under this heuristic; a band
+ * that is asked for is not used (said once on stderr).  NULL: the exact search again.  A bad member (as above), or a span or
+ * two-piece penalties are configured: rejected (-1, message), state unchanged -- as are those while a heuristic is configured. */
+int wfagpu_amd_configure_wfadaptive(const wfagpu_amd_wfadaptive_t* heuristic);
 
 void wfagpu_amd_last_stats(const wfagpu_amd_ctx_t* ctx, wfagpu_amd_stats_t* out);
 

@@ -87,6 +87,10 @@ class Penalties2p(C.Structure):  # wfagpu_amd_penalties2p_t: a gap of n bases co
                 ("gap_extension2", C.c_int)]
 
 
+class WfAdaptive(C.Structure):  # wfagpu_amd_wfadaptive_t: WFA2's wf-adaptive heuristic
+    _fields_ = [("min_wavefront_length", C.c_int), ("max_distance_threshold", C.c_int), ("steps_between_cutoffs", C.c_int)]
+
+
 class Stats(C.Structure):  # wfagpu_amd_stats_t
     _fields_ = [("pack_ms", C.c_float), ("align_ms", C.c_float), ("trace_ms", C.c_float), ("total_ms", C.c_float),
                 ("align_launches", C.c_int), ("cells", C.c_ulonglong), ("arena_units", C.c_ulonglong),
@@ -113,6 +117,7 @@ ABI_SYMBOLS = [
     "wfagpu_host_pack_sequence", "wfagpu_host_pack_sequence_scalar", "wfagpu_host_pack_strip",
     "wfagpu_amd_align_device_span", "wfagpu_amd_configure_span",
     "wfagpu_amd_align_device_2p", "wfagpu_amd_configure_affine2p", "wfagpu_amd_debug_code_objects",
+    "wfagpu_amd_align_device_adaptive", "wfagpu_amd_configure_wfadaptive",
 ]
 
 _lib = None
@@ -156,6 +161,11 @@ def load():
     lib.wfagpu_amd_align_device_2p.restype = C.c_int
     lib.wfagpu_amd_configure_affine2p.argtypes = [C.POINTER(Penalties2p)]
     lib.wfagpu_amd_configure_affine2p.restype = C.c_int
+    lib.wfagpu_amd_align_device_adaptive.argtypes = [C.c_void_p, C.POINTER(Batch), Penalties, C.c_int, C.POINTER(WfAdaptive), C.c_bool, C.c_void_p,
+                                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.wfagpu_amd_align_device_adaptive.restype = C.c_int
+    lib.wfagpu_amd_configure_wfadaptive.argtypes = [C.POINTER(WfAdaptive)]
+    lib.wfagpu_amd_configure_wfadaptive.restype = C.c_int
     lib.wfagpu_amd_debug_code_objects.argtypes = []
     lib.wfagpu_amd_debug_code_objects.restype = C.c_uint
     lib.wfagpu_amd_last_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
@@ -241,6 +251,18 @@ def configure_affine2p(pens=None):
         return
     if lib.wfagpu_amd_configure_affine2p(C.byref(Penalties2p(*[int(v) for v in pens]))) != 0:
         raise ValueError(f"wfagpu_amd_configure_affine2p rejected {tuple(pens)}")
+
+
+def configure_wfadaptive(heuristic=None):
+    """wfagpu_amd_configure_wfadaptive: launch_alignments*, wfagpu_align and the CLI align under WFA2's wf-adaptive heuristic
+    (min_wavefront_length, max_distance_threshold, steps_between_cutoffs).  None: the exact search again.  Raises ValueError when the
+    library rejects it (a bad member, or a span or two-piece penalties are configured)."""
+    lib = load()
+    if heuristic is None:
+        lib.wfagpu_amd_configure_wfadaptive(None)
+        return
+    if lib.wfagpu_amd_configure_wfadaptive(C.byref(WfAdaptive(*[int(v) for v in heuristic]))) != 0:
+        raise ValueError(f"wfagpu_amd_configure_wfadaptive rejected {tuple(heuristic)}")
 
 
 def last_launch_stats():
@@ -501,7 +523,7 @@ class DeviceAligner:
         return d_packed.cpu().numpy().view(np.uint32), d_flags.cpu().numpy()
 
     def align(self, batch, penalties, max_error, compute_cigar, band=-1, band_width=0, fetch=True, d_scores=None, span=None,
-              fetch_ends=False, affine2p=None):
+              fetch_ends=False, affine2p=None, wfadaptive=None):
         """Returns (scores ndarray, cigars list or None).  With fetch=False results stay on the device
         and (d_scores tensor, (text_ptr, off_ptr, len_ptr)) is returned.  d_scores: the caller's int32 device tensor for the scores
         (the C interface takes the caller's buffer: a loop of calls need not allocate one per call).
@@ -509,7 +531,9 @@ class DeviceAligner:
         (wfagpu_amd_align_device_span; exact search, a band is an error).  fetch_ends (span only): a third result, int32[n, 2] =
         the start and end diagonals (k0, k1) of every pair (k0 is INT32_MIN in score-only calls).
         affine2p: (x, o1, e1, o2, e2), two-piece gap-affine penalties (wfagpu_amd_align_device_2p; exact end-to-end search: a band or a
-        span is an error); `penalties` is ignored then."""
+        span is an error); `penalties` is ignored then.
+        wfadaptive: (min_wavefront_length, max_distance_threshold, steps_between_cutoffs), WFA2's wf-adaptive heuristic
+        (wfagpu_amd_align_device_adaptive; end to end, gap-affine: a band, a span or two pieces is an error)."""
         torch = self.torch
         dev = torch.device("cuda", self.device)
         n = batch.num_pairs
@@ -521,6 +545,8 @@ class DeviceAligner:
         span = _as_span(span)
         if affine2p is not None and (span is not None or (band > 0 and band_width > 0)):
             raise ValueError("two-piece penalties are not combined with an ends-free span or the adaptive band")
+        if wfadaptive is not None and (span is not None or affine2p is not None or (band > 0 and band_width > 0)):
+            raise ValueError("the wf-adaptive heuristic is not combined with an ends-free span, two-piece penalties or the adaptive band")
         d_ends = None
         if span is not None:
             if band > 0 and band_width > 0:
@@ -530,7 +556,10 @@ class DeviceAligner:
         elif fetch_ends:
             raise ValueError("fetch_ends needs a span")
         self._inputs_ready()
-        if affine2p is not None:
+        if wfadaptive is not None:
+            rc = self.lib.wfagpu_amd_align_device_adaptive(self.ctx, C.byref(batch), pen, int(max_error), C.byref(WfAdaptive(*[int(v) for v in wfadaptive])),
+                                                           bool(compute_cigar), d_scores.data_ptr(), C.byref(t), C.byref(o), C.byref(l))
+        elif affine2p is not None:
             rc = self.lib.wfagpu_amd_align_device_2p(self.ctx, C.byref(batch), C.byref(Penalties2p(*[int(v) for v in affine2p])), int(max_error),
                                                      bool(compute_cigar), d_scores.data_ptr(), C.byref(t), C.byref(o), C.byref(l))
         elif span is not None:
@@ -542,7 +571,7 @@ class DeviceAligner:
                                                   bool(compute_cigar), d_scores.data_ptr(), C.byref(t), C.byref(o),
                                                   C.byref(l))
         if rc != 0:
-            raise RuntimeError(f"wfagpu_amd_align_device{'_2p' if affine2p is not None else '_span' if span is not None else ''} failed ({rc})")
+            raise RuntimeError(f"wfagpu_amd_align_device{'_adaptive' if wfadaptive is not None else '_2p' if affine2p is not None else '_span' if span is not None else ''} failed ({rc})")
         if not fetch:
             res = (d_scores[:n], (t.value, o.value, l.value))
             return res + (d_ends[:n],) if fetch_ends else res

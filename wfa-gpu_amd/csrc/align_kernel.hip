@@ -65,6 +65,7 @@
 //   align/loop_lean_hbm.inc   lean score loop of the tiers whose ring lives in HBM
 //   align/loop_careful.inc    the careful score step (WFA2 to the letter)
 //   align/loop_careful_2p.inc the careful score step of the two-piece instantiations
+//   align/loop_careful_ad.inc the careful score step of the wf-adaptive instantiations (WFA2's heuristic cut-off)
 //   align/band_window.inc, align/loop_banded.inc   the adaptive band: the reference's window rule, the banded search
 #include <type_traits>
 
@@ -200,13 +201,19 @@ __device__ __forceinline__ ColdParams cold_params() {
 // min(o1 + n e1, o2 + n e2).  Five components per score (M, I1, D1, I2, D2): e2 + 1 rows each of I2 and D2 behind the D ring, a second
 // row book for their limits, seven reads and five stores per cell, origin bytes BT2_* (wfa_device.h); a score step of its own
 // (align/loop_careful_2p.inc: the careful one, WFA2 to the letter), origin bytes in ROWS.  Window and reach: below, where they are derived.
+// ADAPTIVE (align_kernel_ad.hip includes this file for those instantiations): WFA2's wf-adaptive heuristic -- every few scores the
+// diagonals at the ends of the extended M row that lag more than a threshold behind the one closest to the end are dropped
+// (wavefront_heuristic.c:508-561).  A heuristic's rows depend on every cell WFA2 computes, so neither the window nor the reach
+// interval prunes: a row is bounded by the sequences and by the ring (|k| <= (s - o) / e up to score s), M carries WFA2's trimmed
+// limits; a score step of its own (align/loop_careful_ad.inc), origin bytes in ROWS.
 template <int NW, bool BT, typename OffT, bool GLOBAL_RING, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool TIMED = false, bool ENDSFREE = false,
-          bool TWOPIECE = false>
+          bool TWOPIECE = false, bool ADAPTIVE = false>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu((NW == 1 && !BANDED) ? WPE : 1, 8)))
 wfa_align_kernel(const WfaAlignParams p) {
   static_assert(!HYBRID || (!GLOBAL_RING && !BANDED), "the hybrid ring is an exact LDS tier");
   static_assert(!ENDSFREE || (!BANDED && !HYBRID && !TIMED), "ends-free: the exact search of tiers 0, 1, 2 and 3");
   static_assert(!TWOPIECE || (!BANDED && !HYBRID && !TIMED && !ENDSFREE), "two pieces: the end-to-end exact search of tiers 0, 1, 2 and 3");
+  static_assert(!ADAPTIVE || (!BANDED && !HYBRID && !TIMED && !ENDSFREE && !TWOPIECE), "wf-adaptive: end to end, gap-affine, tiers 0, 1, 2 and 3");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NT = NW * 64;
   const int tid = threadIdx.x;
@@ -233,7 +240,7 @@ wfa_align_kernel(const WfaAlignParams p) {
   // of one bump-allocated row per score behind a row table (wfa_device.h).  The backward walk of a 1 kbp alignment then touches ~35
   // cache lines instead of 74 (55 origin bytes on 55 lines + 19 lines of row table: wfa_walk_kernel is bound by random 64-byte
   // accesses), and a score of the lean loops neither sizes, claims nor records a row: no refill test, no row-table entry.
-  constexpr bool TILED = BT && HOT && !HYBRID && NW == 1 && !BANDED && !ENDSFREE && !TWOPIECE;      // (ends-free, two pieces: ROWS in every tier)
+  constexpr bool TILED = BT && HOT && !HYBRID && NW == 1 && !BANDED && !ENDSFREE && !TWOPIECE && !ADAPTIVE;      // (ends-free, two pieces, wf-adaptive: ROWS in every tier)
   const int GZ = BANDED ? 4 * dm + 2 : 0;
   const int x = p.x, oe = p.oe, e = p.e;
   // (TWOPIECE) the second piece; ring rows in all: dm of M, de each of I1 and D1, de2 each of I2 and D2
@@ -275,6 +282,9 @@ wfa_align_kernel(const WfaAlignParams p) {
   book2.reset();
   if constexpr (BOOK_NW == 1 || !TWOPIECE) { book2.I = book2.D = nullptr; }
   else { book2.I = book.D + (bkm + 1); book2.D = book2.I + (bkm + 1); }
+  // (ADAPTIVE, NW > 1) [3][2] reduction slots of the cut-off's scan, behind the row book: rotated and reset like `red`
+  int* red2 = nullptr;
+  if constexpr (ADAPTIVE && NW > 1) red2 = book.D + (bkm + 1);
 
   uint32_t chunk_cur = 0, chunk_left = 0;   // arena units owned by this block
   uint32_t dbg_i = 0;                       // (TIMED: barrier records written by this wave so far)
@@ -348,11 +358,20 @@ wfa_align_kernel(const WfaAlignParams p) {
       // always exists); it bounds the backtrace row table
       long long worst = (long long)x * min(plen, tlen) + (kend ? oe + (long long)e * (abs(kend) - 1) : 0);
       if constexpr (TWOPIECE) worst = (long long)x * min(plen, tlen) + wfa_gap2p(abs(kend), oe, e, oe2, e2);
+      // (ADAPTIVE: the heuristic's answer may cost more than that alignment, but it is an alignment: every operation of its CIGAR uses
+      // up at least one base of the plen + tlen there are -- a gap base one, for at most o + e; a mismatch two, for x -- so no answer
+      // costs more than max(x, o + e) (plen + tlen).  It bounds the row table.)
+      if constexpr (ADAPTIVE) worst = (long long)max(x, oe) * ((long long)plen + tlen);
       budget = (int)min((long long)budget, worst);
     }
     int wlo = -plen, whi = tlen;
     bool feasible = true;
-    if constexpr (TWOPIECE) {
+    if constexpr (ADAPTIVE) {
+      // wf-adaptive: no pruning.  Up to score s WFA2's rows stay within |k| <= (s - o) / e (a diagonal further out needs one more gap
+      // base), so a ring of that many diagonals on either side of 0 holds every row up to the budget; the score step checks it.
+      const long long kmax = budget >= oe ? ((long long)budget - (oe - e)) / e : 0;
+      wlo = -(int)min((long long)plen, kmax); whi = (int)min((long long)tlen, kmax);
+    } else if constexpr (TWOPIECE) {
       // Two pieces.  A gap of n bases costs g(n) = min(o1 + n e1, o2 + n e2), and g is subadditive (wfa_device.h), so a path that visits a
       // diagonal t beyond both 0 and kend holds gaps of at least t + |kend| bases in one direction and t in the other:
       // g(t + |kend|) + g(t) <= S.  The largest such t (wfa_stray2p: a bisection on the scalar unit, once per alignment) on either side
@@ -470,6 +489,7 @@ wfa_align_kernel(const WfaAlignParams p) {
         else { for (int i = tid; i <= bkm; i += NT) { book2.I[i] = book2.D[i] = ROW_NONE_A; } }
       }
       if constexpr (NW > 1) { if (tid < 24) red[tid] = (tid & 7) == 6 ? 0 : (((tid & 7) & 1) ? INT_MIN : INT_MAX); }
+      if constexpr (ADAPTIVE && NW > 1) { if (tid < 6) red2[tid] = (tid & 1) ? INT_MIN : INT_MAX; }
       block_sync<NW>();
 
       // A fresh chunk of the backtrace arena for this workgroup, at least `units` (16-byte units) long: one returning
@@ -576,6 +596,14 @@ wfa_align_kernel(const WfaAlignParams p) {
       }
       const bool touched_at_0 = (d0 & 2u) != 0;
       block_sync<NW>();
+      // (ADAPTIVE) steps_wait: scores with an M row until the next cut-off is due (wavefront_heuristic.c:114-117; it keeps running down
+      // while rows are too short).  The cut-off runs at score 0 too (wavefront_extend.c:345-355): one cell, nothing to drop.
+      // null_steps: consecutive scores without a wavefront -- more than the ring is deep: WFA2's "unfeasible".
+      int steps_wait = 0, null_steps = 0;
+      if constexpr (ADAPTIVE) {
+        steps_wait = p.ad_steps;
+        if (!done) { --steps_wait; if (steps_wait <= 0 && 1 >= p.ad_min_len) steps_wait = p.ad_steps; }
+      }
 
       // Ring state of score s, as row pointers that advance by one row per score (no multiply, no modulo
       // in the loop): the M rows of s, s-x, s-(o+e) and the I rows of s, s-e (the D ring sits de rows
@@ -663,6 +691,8 @@ wfa_align_kernel(const WfaAlignParams p) {
       if (!done && status == WFA_ST_DONE) for (;;) {
         if constexpr (TWOPIECE) {
           #include "align/loop_careful_2p.inc"
+        } else if constexpr (ADAPTIVE) {
+          #include "align/loop_careful_ad.inc"
         } else {
           #include "align/loop_banded.inc"
           #include "align/loop_lean_e1.inc"
@@ -698,9 +728,10 @@ wfa_align_kernel(const WfaAlignParams p) {
   }
 }
 
-template <int NW, bool BT, typename OffT, bool GR, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool TIMED = false, bool EF = false, bool TP = false>
+template <int NW, bool BT, typename OffT, bool GR, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool TIMED = false, bool EF = false, bool TP = false,
+          bool AD = false>
 void launch_inst(const WfaAlignParams& p, size_t lds, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
-  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE, TIMED, EF, TP>;
+  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE, TIMED, EF, TP, AD>;
   // the opt-in for large dynamic LDS is sticky per device and per kernel: pay the driver call once
   static thread_local size_t allowed[16] = {0};
   int dev = 0;
@@ -712,9 +743,9 @@ void launch_inst(const WfaAlignParams& p, size_t lds, int grid, hipStream_t stre
   wfa_launch_timed(k, dim3(grid), dim3(NW * 64), lds, stream, ev0, ev1, p);
 }
 
-template <int NW, bool BT, typename OffT, bool GR, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool EF = false, bool TP = false>
+template <int NW, bool BT, typename OffT, bool GR, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool EF = false, bool TP = false, bool AD = false>
 int occ_inst(size_t lds) {
-  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE, false, EF, TP>;
+  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE, false, EF, TP, AD>;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   int nb = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), NW * 64, lds) != hipSuccess) {
@@ -724,7 +755,49 @@ int occ_inst(size_t lds) {
   return nb;
 }
 
-#if defined(WFA_ALIGN_TWOPIECE_UNIT)
+#if defined(WFA_ALIGN_ADAPTIVE_UNIT)
+// ---- the wf-adaptive translation unit (align_kernel_ad.hip): tiers 0, 1, 2 and 3, with and without backtrace, packed and byte-compare
+template <bool BT, bool RAW>
+void launch_tier_ad(const WfaAlignParams& p, int tier, size_t lds, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  switch (tier) {
+    case 0: launch_inst<1, BT, int16_t, false, RAW, false, false, 8, false, false, false, true>(p, lds, grid, stream, ev0, ev1); break;
+    case 1: launch_inst<4, BT, int16_t, false, RAW, false, false, 8, false, false, false, true>(p, lds, grid, stream, ev0, ev1); break;
+    case 2: launch_inst<16, BT, int16_t, false, RAW, false, false, 8, false, false, false, true>(p, lds, grid, stream, ev0, ev1); break;
+    default:
+      if (p.ring16) launch_inst<16, BT, int16_t, true, RAW, false, false, 8, false, false, false, true>(p, lds, grid, stream, ev0, ev1);
+      else launch_inst<16, BT, int32_t, true, RAW, false, false, 8, false, false, false, true>(p, lds, grid, stream, ev0, ev1);
+      break;
+  }
+}
+template <bool BT, bool RAW>
+int occ_tier_ad(int tier, size_t lds) {
+  switch (tier) {
+    case 0: return occ_inst<1, BT, int16_t, false, RAW, false, false, 8, false, false, true>(lds);
+    case 1: return occ_inst<4, BT, int16_t, false, RAW, false, false, 8, false, false, true>(lds);
+    case 2: return occ_inst<16, BT, int16_t, false, RAW, false, false, 8, false, false, true>(lds);
+    default: return occ_inst<16, BT, int32_t, true, RAW, false, false, 8, false, false, true>(lds);
+  }
+}
+
+}  // namespace
+
+void wfa_launch_align_ad(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  wfa_unit_entered(WFA_UNIT_ALIGN_AD);
+  const size_t lds = wfa_align_lds_bytes(p, tier);
+  if (with_bt) { if (raw) launch_tier_ad<true, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_ad<true, false>(p, tier, lds, grid, stream, ev0, ev1); }
+  else { if (raw) launch_tier_ad<false, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_ad<false, false>(p, tier, lds, grid, stream, ev0, ev1); }
+}
+
+int wfa_align_ad_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds) {
+  wfa_unit_entered(WFA_UNIT_ALIGN_AD);
+  if (with_bt) return raw ? occ_tier_ad<true, true>(tier, lds) : occ_tier_ad<true, false>(tier, lds);
+  return raw ? occ_tier_ad<false, true>(tier, lds) : occ_tier_ad<false, false>(tier, lds);
+}
+
+// (this code object is loaded by the first launch of one of its kernels: wfagpu_amd_prime does that only under a configured heuristic)
+namespace { __global__ void k_prime_align_ad() {} }
+void wfa_prime_align_ad(hipStream_t stream) { wfa_unit_entered(WFA_UNIT_ALIGN_AD); hipLaunchKernelGGL(k_prime_align_ad, dim3(1), dim3(64), 0, stream); }
+#elif defined(WFA_ALIGN_TWOPIECE_UNIT)
 // ---- the two-piece translation unit (align_kernel_2p.hip): tiers 0, 1, 2 and 3, with and without backtrace, packed and byte-compare
 template <bool BT, bool RAW>
 void launch_tier_2p(const WfaAlignParams& p, int tier, size_t lds, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
@@ -886,7 +959,8 @@ size_t wfa_align_lds_bytes(const WfaAlignParams& p, int tier) {
   const size_t seq = (size_t)2 * p.seq_words_cap * 4;
   // reduction slots [24] + broadcast [2] + (NW > 1) row book [3][book]
   const size_t bk = (size_t)p.book_mask + 1;
-  const size_t meta = (size_t)(24 + 2 + ((tier == 0 || p.band_width > 0) ? 0 : (p.e2 > 0 ? 5 : 3) * bk)) * 4;     // (tiers 1, 2, 3, 4 of the exact search: row book in LDS; two pieces: I2 and D2 too)
+  // (wf-adaptive, p.ad_steps > 0: eight words more behind the book, the reduction slots of the cut-off's scan)
+  const size_t meta = (size_t)(24 + 2 + ((tier == 0 || p.band_width > 0) ? 0 : (p.e2 > 0 ? 5 : 3) * bk + (p.ad_steps > 0 ? 8 : 0))) * 4;    // (tiers 1, 2, 3, 4 of the exact search: row book in LDS; two pieces: I2 and D2 too)
   return ((ring + seq + meta) + 15) & ~(size_t)15;
 }
 

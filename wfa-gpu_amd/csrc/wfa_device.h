@@ -163,6 +163,9 @@ struct WfaAlignParams {
   // two-piece gap-affine (only the TWOPIECE instantiations, align_kernel_2p.hip, read these; e2 == 0: gap-affine): the second piece as
   // open + extend and extend, e2 + 1 rows each of I2 and D2 behind the D ring.  x / oe / e / de are the first piece, dm = max(x, oe, oe2) + 1.
   int oe2, e2, de2;
+  // wf-adaptive (only the ADAPTIVE instantiations, align_kernel_ad.hip, read these; ad_steps == 0: exact search): WFA2's
+  // min_wavefront_length, max_distance_threshold, steps_between_cutoffs
+  int ad_min_len, ad_max_dist, ad_steps;
 };
 
 struct WfaTraceParams {
@@ -261,6 +264,18 @@ void wfa_prime_align_2p(hipStream_t stream);
 // wfagpu_amd_align_device call to run under (nullptr: gap-affine), as five ints.
 bool wfa_configured_affine2p(int* out5);
 const int* wfa_lane_affine2p5();
+// The wf-adaptive instantiations (align_kernel_ad.hip: a code object of their own, loaded only by calls under the heuristic): tiers 0,
+// 1, 2 and 3, careful loop with WFA2's cut-off, origin bytes in ROWS; the gap-affine backtrace kernels serve them as they are.
+// wfa_align_lds_bytes serves them too (WfaAlignParams::ad_steps > 0).
+void wfa_launch_align_ad(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream,
+                         hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+int wfa_align_ad_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds_bytes);
+void wfa_prime_align_ad(hipStream_t stream);
+// The heuristic of wfagpu_amd_configure_wfadaptive (wfa_launch.hip): false when none is configured; out (optional) receives
+// {min_wavefront_length, max_distance_threshold, steps_between_cutoffs}.  wfa_lane_wfadaptive3: what the calling thread -- a lane of
+// launch_alignments* -- wants its wfagpu_amd_align_device call to run under (nullptr: exact), as three ints.
+bool wfa_configured_wfadaptive(int* out3);
+const int* wfa_lane_wfadaptive3();
 bool wfa_launch_trace(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);     // false: nothing to launch
 // (the backtrace of two-piece alignments: trace_kernel_2p.hip, the same kernels compiled for five walk states and BT2_* origin bytes)
 bool wfa_launch_trace_2p(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
@@ -281,7 +296,7 @@ const WfaShortEntry* wfa_short_entry_e4(int ascii, int bt, int l32, int idx);
 // Which of the optional code objects -- the ones only some callers load -- this process has entered: every host function that launches,
 // queries or primes a kernel of such a unit says so (the runtime loads a code object at the first of these).  Process-wide, never
 // cleared; wfagpu_amd_debug_code_objects() (wfa_host.hip) hands the bits out, tests check "never loaded" with them.
-enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u };
+enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u, WFA_UNIT_ALIGN_AD = 8u };
 void wfa_unit_entered(unsigned unit);
 // Code-object priming: one empty launch per kernel translation unit (see the definitions).
 void wfa_prime_pack(hipStream_t stream);

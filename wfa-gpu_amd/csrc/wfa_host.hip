@@ -511,6 +511,7 @@ int wfagpu_amd_prime(wfagpu_amd_ctx_t* c) {
   wfa_prime_short(c->stream);
   if (wfa_configured_span(nullptr)) wfa_prime_align_ef(c->stream);      // (the ends-free kernels: only callers under a span load them)
   if (wfa_configured_affine2p(nullptr)) { wfa_prime_align_2p(c->stream); wfa_prime_trace_2p(c->stream); }  // (the two-piece kernels: only callers under such penalties)
+  if (wfa_configured_wfadaptive(nullptr)) wfa_prime_align_ad(c->stream);      // (the wf-adaptive kernels: only callers under the heuristic)
   LAUNCH_K(k_iota, dim3(1), dim3(64), 0, c->stream, static_cast<uint32_t*>(nullptr), 0u, 0u);      // (this file's)
   HIP_TRY(hipGetLastError());
   c->primed = true;
@@ -553,6 +554,14 @@ int window_width_2p(long long S, const WfaAlignParams& p, unsigned max_seq_len) 
   const long long all = 2ll * max_seq_len + 1;
   if (S >= INT_MAX / 2) return (int)all;
   return (int)std::max<long long>(1, std::min<long long>(all, wfa_reach2p(S, p.oe, p.e, p.oe2, p.e2) + 3));
+}
+
+// The same under the wf-adaptive heuristic (the kernel's ring): nothing is pruned, up to score S WFA2's rows stay within
+// |k| <= (S - o) / e on either side of diagonal 0 -- about twice the exact search's window.
+int window_width_ad(long long S, int o, int e, unsigned max_seq_len) {
+  const long long all = 2ll * max_seq_len + 1;
+  if (S >= INT_MAX / 2) return (int)all;
+  return (int)std::max<long long>(1, std::min<long long>(all, 2 * (S >= o + e ? (S - o) / e : 0) + 1));
 }
 
 // Smallest tier whose LDS footprint fits a score budget S.
@@ -600,8 +609,9 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   // free bases (clamped to the sequences).  A bound for the longest pair, not an exact figure: a pair whose own window is wider
   // comes back as a BAND failure and is escalated like any other.  Tiers 0, 1, 2 and 3 only.
   // Two pieces (p.e2 > 0): tiers 0, 1, 2 and 3 of the exact search, like ends-free; never combined with it.
-  const bool ef = p.ends != nullptr, tp2 = p.e2 > 0;
-  int width = tp2 ? window_width_2p(max_score, p, max_seq_len) : window_width(max_score, p.oe - p.e, p.e, max_seq_len);
+  // wf-adaptive (p.ad_steps > 0): tiers 0, 1, 2 and 3 likewise, rings sized by window_width_ad; never combined with either.
+  const bool ef = p.ends != nullptr, tp2 = p.e2 > 0, ad = p.ad_steps > 0;
+  int width = ad ? window_width_ad(max_score, p.oe - p.e, p.e, max_seq_len) : tp2 ? window_width_2p(max_score, p, max_seq_len) : window_width(max_score, p.oe - p.e, p.e, max_seq_len);
   if (ef) {
     const long long m = max_seq_len;
     const long long free_sum = std::min<long long>(p.span_pbf, m) + std::min<long long>(p.span_pef, m) + std::min<long long>(p.span_tbf, m) + std::min<long long>(p.span_tef, m);
@@ -610,7 +620,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   // Short wavefronts, score only (tier 5, short_kernel.hip): when the diagonal window of the budget fits 16 or 32 lanes, four or two
   // alignments share a wavefront and the rings live in registers (BASELINE configs[1]: 150 bp reads, budgets of ~14 once
   // they are tuned).  Pairs whose own window is wider (large |tlen - plen|) come back as BAND failures and go on as always.
-  if (!ef && !tp2 && !raw && !(p.ascii && !c->short_ascii_ok) && c->tuning.min_tier == 0 && !(bt && c->tuning.no_short_cigar) && wfa_short_supported(p.x, p.oe, p.e) && width + 1 <= 32 && max_score <= 30000) {
+  if (!ef && !tp2 && !ad && !raw && !(p.ascii && !c->short_ascii_ok) && c->tuning.min_tier == 0 && !(bt && c->tuning.no_short_cigar) && wfa_short_supported(p.x, p.oe, p.e) && width + 1 <= 32 && max_score <= 30000) {
     const int lanes = width + 1 <= 16 ? 16 : 32;
     p.rs = 0;
     const size_t lds = wfa_short_lds_bytes(p, lanes, bt);
@@ -638,13 +648,13 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     if (t == 0 && (width > 1024 || p.dm > 64)) continue;
     if (t == 1 && width > 8192) continue;
     if (t == 1 && few_pairs && width >= 1024 && !min_tier && wfa_align_lds_bytes(p, 2) <= budget[2]) continue;
-    int nb = tp2 ? wfa_align_2p_max_blocks_per_cu(t, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(t, bt, raw, lds) : wfa_align_max_blocks_per_cu(t, bt, raw, false, lds);
+    int nb = ad ? wfa_align_ad_max_blocks_per_cu(t, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(t, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(t, bt, raw, lds) : wfa_align_max_blocks_per_cu(t, bt, raw, false, lds);
     if (nb < 1) continue;
     // Occupancy-matched instantiation of the one-wave kernels: LDS decides how many rings a CU holds; compiled for 8 waves
     // per SIMD the kernel lives on 64 VGPRs and 78 SGPRs (123 scalar spills + scratch), which only pays when 8 waves per
     // SIMD really are resident.  The smallest of 4 / 6 / 7 / 8 that keeps all the rings LDS allows but at most one.
     int wpe = 8;
-    if (t == 0 && !raw && !ef && !tp2) {
+    if (t == 0 && !raw && !ef && !tp2 && !ad) {
       const int forced = c->tuning.waves_per_simd;
       for (int w : {4, 6, 7, 8}) if (4 * w >= nb - 1) { wpe = w; break; }
       // (gap extensions > 1: the general lean loop carries more scalar state than the e == 1 loop; compiled for 8 waves per SIMD -- 64
@@ -662,7 +672,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     // (profiles/r02/mid_lengths.txt).  tuning.t0_min_blocks: A/B.
     const int t0_min_blocks = c->tuning.t0_min_blocks > 0 ? c->tuning.t0_min_blocks : 10;
     if (t == 0 && !min_tier && nb < t0_min_blocks && width >= 384) continue;
-    if (t == 1 && !raw && !ef && !tp2 && c->tuning.exact_two_waves) {
+    if (t == 1 && !raw && !ef && !tp2 && !ad && c->tuning.exact_two_waves) {
       // A/B hook: TWO waves per alignment where four would run (same ring, same LDS; half the per-score bookkeeping per chunk, half the waves)
       const size_t lds2 = wfa_align_lds_bytes(p, 6);
       const int nb2 = wfa_align_max_blocks_per_cu(6, bt, raw, false, lds2);
@@ -672,7 +682,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     return true;
   }
   // hybrid ring: everything but the D rows in LDS (one workgroup of 16 waves per CU)
-  if (i16_ok && !raw && !ef && !tp2 && min_tier != 3) {
+  if (i16_ok && !raw && !ef && !tp2 && !ad && min_tier != 3) {
     const size_t lds_h = wfa_align_lds_bytes(p, 4);
     if (lds_h <= c->lds_per_block_max) {
       const int nb = wfa_align_max_blocks_per_cu(4, bt, raw, false, lds_h);
@@ -682,7 +692,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   p.rs = rs_plain;
   const size_t lds = wfa_align_lds_bytes(p, 3);
   if (lds > c->lds_per_block_max) return false;   // sequences themselves do not fit LDS
-  const int nb = tp2 ? wfa_align_2p_max_blocks_per_cu(3, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(3, bt, raw, lds) : wfa_align_max_blocks_per_cu(3, bt, raw, false, lds);
+  const int nb = ad ? wfa_align_ad_max_blocks_per_cu(3, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(3, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(3, bt, raw, lds) : wfa_align_max_blocks_per_cu(3, bt, raw, false, lds);
   *out = {3, width, max_score, lds, std::max(1, std::min(nb, 2))};
   return true;
 }
@@ -714,11 +724,19 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
                              bool compute_cigar, int32_t* d_scores,
                              const char** d_text, const unsigned long long** d_off,
                              const unsigned int** d_len, const wfagpu_amd_span_t* span, int32_t* d_ends,
-                             const wfagpu_amd_penalties2p_t* pen2 = nullptr) {
+                             const wfagpu_amd_penalties2p_t* pen2 = nullptr, const wfagpu_amd_wfadaptive_t* wfad = nullptr) {
   if (!c || !b || !d_scores) return -1;
   const bool ef = span != nullptr;
   const bool tp2 = pen2 != nullptr;
-  if (ef || tp2) { band = -1; band_width = 0; }      // (exact search: a band is a permission to approximate, not an obligation)
+  // wfad != nullptr: WFA2's wf-adaptive heuristic (align_kernel_ad.hip), end to end, gap-affine
+  const bool ad = wfad != nullptr;
+  if (ad && (ef || tp2)) { fprintf(stderr, "[!] ERROR: the wf-adaptive heuristic is not combined with an ends-free span or two-piece penalties\n"); return -1; }
+  if (ad && (wfad->min_wavefront_length < 1 || wfad->max_distance_threshold < 0 || wfad->steps_between_cutoffs < 1)) {
+    fprintf(stderr, "[!] ERROR: wf-adaptive takes min_wavefront_length >= 1, max_distance_threshold >= 0, steps_between_cutoffs >= 1 (got %d,%d,%d)\n",
+            wfad->min_wavefront_length, wfad->max_distance_threshold, wfad->steps_between_cutoffs);
+    return -1;
+  }
+  if (ef || tp2 || ad) { band = -1; band_width = 0; }      // (exact search: a band is a permission to approximate, not an obligation; wf-adaptive: its own heuristic)
   if (tp2 && ef) { fprintf(stderr, "[!] ERROR: two-piece penalties are not combined with an ends-free span\n"); return -1; }
   int o2 = 0, e2 = 0;      // the second piece (pen holds x and the first)
   if (tp2) {
@@ -813,6 +831,9 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
   ap.dm = std::max(pen.x, oe) + 1;
   ap.de = pen.e + 1;
   if (tp2) { ap.oe2 = o2 + e2; ap.e2 = e2; ap.de2 = e2 + 1; ap.dm = std::max(ap.dm, ap.oe2 + 1); }
+  // (wf-adaptive under penalties reduced by their common factor: scores that are no multiple of it have no wavefront, and WFA2's
+  // cut-off does not count those -- the same rows are cut)
+  if (ad) { ap.ad_min_len = wfad->min_wavefront_length; ap.ad_max_dist = wfad->max_distance_threshold; ap.ad_steps = wfad->steps_between_cutoffs; }
   // every operation of an alignment costs at least this much (sizes the op lists and texts of the backtrace)
   const int min_op_cost = tp2 ? std::min(pen.x, std::min(pen.e, e2)) : std::min(pen.x, pen.e);
   { int bk = 64; while (bk < ap.dm) bk <<= 1; ap.book_mask = bk - 1; }
@@ -839,7 +860,12 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
     if (w > 1024) return 0.0;      // (wider wavefronts run on the multi-wave tiers: rows behind a row table)
     return 64.0 * (double)((w + 15) / 16) * (double)(B / 4 + 1) + 512.0;
   };
-  if (!tp2) est_pair_bytes = std::max(est_pair_bytes, tiled_pair_bytes(std::min<long long>(max_error, 2ll * batch_max_len * std::max(pen.x, pen.e))));
+  if (ad) {
+    // (wf-adaptive: rows behind a row table in every tier; nothing is pruned, so until the cut-off bites a row gains two diagonals
+    // every e scores and loses none: B^2 / e bytes under a budget B -- an upper estimate, refined after every pass)
+    const double B = std::min<unsigned>(max_error, 2 * max_len);
+    est_pair_bytes = (B + 1) * (B + 1) / pen.e + 16.0 * B + 4096.0;
+  } else if (!tp2) est_pair_bytes = std::max(est_pair_bytes, tiled_pair_bytes(std::min<long long>(max_error, 2ll * batch_max_len * std::max(pen.x, pen.e))));
   else {
     // (two pieces: one byte per cell of the two-piece diamond -- rows behind a row table in every tier.  The wavefront gains a diagonal on
     // each side every min(e1, e2) scores and the reach takes them back at the same rate: B^2 / (2 min(e1, e2)) cells under a budget B)
@@ -885,7 +911,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
   // 18 us + the gap between two launches of a 168 us step of 100k configs[1] pairs.  (ASCII dword indices are 32-bit there.)
   // (sequences_bytes may be missing from a caller's batch record: four times the packed words bound the ASCII layout from above)
   c->short_ascii_ok = std::max<size_t>(b->sequences_bytes, b->packed_bytes * 4) < ((size_t)1 << 34);
-  const bool short_fuses = !ef && !tp2 && wfa_short_supported(pen.x, oe, pen.e) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
+  const bool short_fuses = !ef && !tp2 && !ad && wfa_short_supported(pen.x, oe, pen.e) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
   const bool fused_pack = !prepacked && (b->max_seq_len >= 512u || short_fuses) && !c->tuning.no_fused_pack;
   // Every status starts as PENDING = 0: written by the pack kernel where it runs (it visits every pair anyway), by a memset (a
   // launch of its own, ~5 us + a gap) where it does not -- queued by whoever reads the array first (ensure_status), and not at all
@@ -1141,6 +1167,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
         }
         else if (ef) wfa_launch_align_ef(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else if (tp2) wfa_launch_align_2p(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
+        else if (ad) wfa_launch_align_ad(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else wfa_launch_align(ap, tp.tier, cigar_now, raw, grid, st, tp.wpe, L.e0, L.e1);
         {
           const hipError_t le = hipGetLastError();
@@ -1177,7 +1204,8 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
         if (!(L.budgeted && n_links == 1 && speculate)) break;
       }
       // (whatever the budget, no optimal alignment costs more than mismatching the shorter sequence and one gap for the rest)
-      s_hi = std::min<long long>(s_hi, (long long)pen.x * max_len + oe + (long long)pen.e * max_len);
+      // (wf-adaptive: the heuristic's answer may cost more; the kernel's bound: no alignment costs more than max(x, o + e) per base)
+      s_hi = std::min<long long>(s_hi, ad ? 2ll * std::max(pen.x, oe) * max_len : (long long)pen.x * max_len + oe + (long long)pen.e * max_len);
       // ---- backtrace + CIGAR for everything of the chain's list that finished -----------------------------------------
       if (zero_counter(c, CT_SUM_OPS, 2)) return -1;
       if (zero_counter(c, CT_OPS)) return -1;
@@ -1388,7 +1416,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
       // (tuned budgets pay where they narrow a wide window -- or, score-only, where they bring it down to what the
       // several-alignments-per-wavefront tier holds)
       const bool short_ok = wfa_short_supported(pen.x, oe, pen.e) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar);
-      const bool would_tune = !ef && !tp2 && n >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) && (w_me > 128 || (w_me > 15 && short_ok));
+      const bool would_tune = !ef && !tp2 && !ad && n >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) && (w_me > 128 || (w_me > 15 && short_ok));
       bool inherited = false;
       if (would_tune && c->same_stream)
         for (int i = 0; i < c->n_saved_q; ++i) {
@@ -1435,7 +1463,8 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
       // (the budgets decide whether the band is worth using and serve the exact kernels; with the band forced neither applies)
       // (ends-free: no budgets from a sample -- the careful loop is the only one, and a read's score says little about a window's)
       // (two pieces: none either -- switched off, not tuned: DESIGN.md section 4.7)
-      const bool try_budget = !ef && !tp2 && !raw && n_pending >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) &&
+      // (wf-adaptive: none either -- a budget from the exact scores of a sample says nothing about the heuristic's)
+      const bool try_budget = !ef && !tp2 && !ad && !raw && n_pending >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) &&
                               (w_me2 > 128 || (w_me2 > 15 && short_ok2));
       int saved_idx = -1;
       if (try_budget && c->same_stream) {
@@ -1606,7 +1635,20 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
     const wfagpu_amd_penalties2p_t p2{l2[0], l2[1], l2[2], l2[3], l2[4]};
     return align_device_impl(c, b, pen, max_error, band, band_width, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, &p2);
   }
+  // (and for a configured wf-adaptive heuristic: wfagpu_amd_configure_wfadaptive)
+  const int* const la = wfa_lane_wfadaptive3();
+  if (la) {
+    const wfagpu_amd_wfadaptive_t h{la[0], la[1], la[2]};
+    return align_device_impl(c, b, pen, max_error, band, band_width, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, nullptr, &h);
+  }
   return align_device_impl(c, b, pen, max_error, band, band_width, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr);
+}
+
+extern "C" int wfagpu_amd_align_device_adaptive(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b, affine_penalties_t pen, int max_error,
+                                                const wfagpu_amd_wfadaptive_t* heuristic, bool compute_cigar, int32_t* d_scores,
+                                                const char** d_text, const unsigned long long** d_off, const unsigned int** d_len) {
+  // (NULL: the exact end-to-end search, whatever is configured for the lanes)
+  return align_device_impl(c, b, pen, max_error, -1, 0, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, nullptr, heuristic);
 }
 
 extern "C" int wfagpu_amd_align_device_2p(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b, const wfagpu_amd_penalties2p_t* pens, int max_error,

@@ -56,7 +56,36 @@ thread_local const int* t_lane_span = nullptr;
 bool g_2p_set = false;
 int g_2p[5] = {0, 0, 0, 0, 0};
 thread_local const int* t_lane_2p = nullptr;
+// The process-wide wf-adaptive heuristic (wfagpu_amd_configure_wfadaptive), the same way (wfa_lane_wfadaptive3); under the same
+// mutex: never configured together with a span or two-piece penalties.
+bool g_ad_set = false;
+int g_ad[3] = {0, 0, 0};
+thread_local const int* t_lane_ad = nullptr;
 }  // namespace
+
+bool wfa_configured_wfadaptive(int* out3) {
+  std::lock_guard<std::mutex> lock(g_span_mutex);
+  if (out3 && g_ad_set) for (int i = 0; i < 3; ++i) out3[i] = g_ad[i];
+  return g_ad_set;
+}
+const int* wfa_lane_wfadaptive3() { return t_lane_ad; }
+
+extern "C" int wfagpu_amd_configure_wfadaptive(const wfagpu_amd_wfadaptive_t* h) {
+  if (h && (h->min_wavefront_length < 1 || h->max_distance_threshold < 0 || h->steps_between_cutoffs < 1)) {
+    fprintf(stderr, "[!] ERROR: wf-adaptive takes min_wavefront_length >= 1, max_distance_threshold >= 0, steps_between_cutoffs >= 1 (got %d,%d,%d)\n",
+            h->min_wavefront_length, h->max_distance_threshold, h->steps_between_cutoffs);
+    return -1;
+  }
+  std::lock_guard<std::mutex> lock(g_span_mutex);
+  if (h && (g_span_set || g_2p_set)) {
+    fprintf(stderr, "[!] ERROR: the wf-adaptive heuristic is not combined with an ends-free span or two-piece penalties (%s configured)\n",
+            g_span_set ? "a span is" : "they are");
+    return -1;
+  }
+  g_ad_set = h != nullptr;
+  if (h) { g_ad[0] = h->min_wavefront_length; g_ad[1] = h->max_distance_threshold; g_ad[2] = h->steps_between_cutoffs; }
+  return 0;
+}
 
 bool wfa_configured_span(int* out4) {
   std::lock_guard<std::mutex> lock(g_span_mutex);
@@ -82,6 +111,10 @@ extern "C" int wfagpu_amd_configure_affine2p(const wfagpu_amd_penalties2p_t* pen
     fprintf(stderr, "[!] ERROR: two-piece penalties are not combined with an ends-free span (one is configured)\n");
     return -1;
   }
+  if (pens && g_ad_set) {
+    fprintf(stderr, "[!] ERROR: two-piece penalties are not combined with the wf-adaptive heuristic (it is configured)\n");
+    return -1;
+  }
   g_2p_set = pens != nullptr;
   if (pens) { g_2p[0] = pens->mismatch; g_2p[1] = pens->gap_opening1; g_2p[2] = pens->gap_extension1; g_2p[3] = pens->gap_opening2; g_2p[4] = pens->gap_extension2; }
   return 0;
@@ -96,6 +129,10 @@ extern "C" int wfagpu_amd_configure_span(const wfagpu_amd_span_t* span) {
   std::lock_guard<std::mutex> lock(g_span_mutex);
   if (span && g_2p_set) {
     fprintf(stderr, "[!] ERROR: an ends-free span is not combined with two-piece penalties (they are configured)\n");
+    return -1;
+  }
+  if (span && g_ad_set) {
+    fprintf(stderr, "[!] ERROR: an ends-free span is not combined with the wf-adaptive heuristic (it is configured)\n");
     return -1;
   }
   g_span_set = span != nullptr;
@@ -233,6 +270,11 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
   // (under configured two-piece penalties: a gap run priced by the cheaper piece, the score checked against the five-table program)
   int q5[5] = {0, 0, 0, 0, 0};
   const int* const p2 = wfa_configured_affine2p(q5) ? q5 : nullptr;
+  // (under a configured wf-adaptive heuristic: the CIGAR is valid and costs the score as always; the score may lie ABOVE the CPU
+  // scorer's optimum -- such pairs are counted and said, they are no failures; a score below the optimum is one)
+  const bool heuristic = wfa_configured_wfadaptive(nullptr);
+  std::atomic<long> above{0};
+  std::atomic<long long> excess{0};
   auto worker = [&](unsigned) {
     verification_scratch_t scratch = {nullptr, 0};     // this worker's, for all its pairs; freed below
     for (;;) {
@@ -261,7 +303,9 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
                                                                    a.opt.penalties.o, a.opt.penalties.e, span, &scratch)
                              : verification_cpu_score_scratch(pattern, text, m.pattern_len, m.text_len, a.opt.penalties.x,
                                                               a.opt.penalties.o, a.opt.penalties.e, &scratch);
-        if (cpu != dist) { LOG_ERROR("Incorrect distance (%ld). GPU=%d, CPU=%d", i, dist, cpu); ok = false; }
+        const int verdict = heuristic ? verification_heuristic_verdict(dist, cpu) : 0;
+        if (verdict > 0) { ++above; excess += verdict; }
+        else if (cpu != dist) { LOG_ERROR("Incorrect distance (%ld). GPU=%d, CPU=%d", i, dist, cpu); ok = false; }
         sum += dist;
         if (ok) ++correct; else ++incorrect;
       }
@@ -275,6 +319,7 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
   parallel_for(nt, worker);
   fprintf(stderr, "(Batch %d) correct=%ld Incorrect=%ld Average score=%f\n", batch_idx, correct.load(), incorrect.load(),
           (to > from) ? (double)sum.load() / (double)(to - from) : 0.0);
+  if (heuristic) fprintf(stderr, "(Batch %d) wf-adaptive: %ld pairs above the optimum (excess %lld in all)\n", batch_idx, above.load(), excess.load());
   g_check_failures += incorrect.load();
   return incorrect.load() ? 1 : 0;
 }
@@ -964,10 +1009,19 @@ int run_device(const CallArgs& a, Shard& sh) {
         }
       }
       t_lane_2p = under_2p ? q5 : nullptr;
+      // (and for a configured wf-adaptive heuristic -- wfagpu_amd_configure_wfadaptive --: a band is not used, said once)
+      int h3[3];
+      const bool under_ad = wfa_configured_wfadaptive(h3);
+      if (under_ad && a.opt.band > 0 && a.opt.threads_per_block > 0) {
+        static std::atomic<bool> warned3{false};
+        if (!warned3.exchange(true)) fprintf(stderr, "[!] WARNING: the adaptive band is not combined with the wf-adaptive heuristic: running under the heuristic alone\n");
+      }
+      t_lane_ad = under_ad ? h3 : nullptr;
       const int arc = wfagpu_amd_align_device(L.ctx, &wb, a.opt.penalties, a.opt.max_error, a.opt.band, a.opt.threads_per_block, a.cigar,
                                               d_sc, &bo.d_text, &bo.d_off, &bo.d_len);
       t_lane_span = nullptr;
       t_lane_2p = nullptr;
+      t_lane_ad = nullptr;
       if (arc) return arc;
       bo.d_scores = d_sc;
       if (a.cigar) { wfagpu_amd_stats_t stt; wfagpu_amd_last_stats(L.ctx, &stt); bo.text_bytes = stt.text_bytes; }

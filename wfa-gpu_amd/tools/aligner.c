@@ -61,6 +61,8 @@ static void usage(const char* prog) {
            "\t                                  begin / end and the text's begin / end (exact search: not with -B)\n"
            "\t    --affine2p <x,o1,e1,o2,e2>    Two-piece gap-affine penalties: a gap of n bases costs min(o1+n*e1, o2+n*e2)\n"
            "\t                                  (WFA2's defaults: 4,6,2,24,1; exact search: not with -g, -B or --ends-free)\n"
+           "\t    --wfa-adaptive <len,dist,steps> WFA2's wf-adaptive heuristic: min_wavefront_length, max_distance_threshold,\n"
+           "\t                                  steps_between_cutoffs (WFA2's defaults: 10,50,1; not with -B, --ends-free or --affine2p)\n"
            "[System]\n"
            "\t-t, --threads-per-block <int>     Accepted for compatibility (band width in banded mode)\n"
            "\t-w, --workers <int>               Accepted for compatibility\n"
@@ -83,12 +85,14 @@ int main(int argc, char** argv) {
         {"batch-size", required_argument, 0, 'b'}, {"band", required_argument, 0, 'B'},
         {"check", no_argument, 0, 'c'}, {"threads-per-block", required_argument, 0, 't'},
         {"workers", required_argument, 0, 'w'}, {"help", no_argument, 0, 'h'}, {"stage-times", no_argument, 0, 1000},
-        {"ends-free", required_argument, 0, 1001}, {"affine2p", required_argument, 0, 1002}, {0, 0, 0, 0}};
+        {"ends-free", required_argument, 0, 1001}, {"affine2p", required_argument, 0, 1002},
+        {"wfa-adaptive", required_argument, 0, 1003}, {0, 0, 0, 0}};
     const char *seq_path = NULL, *q_path = NULL, *t_path = NULL, *out_path = NULL, *pen_str = NULL;
     long n_read = 0, max_distance = -1, batch_size = -1, band_arg = -2, tpb = -1, workers = -1;
     bool print_out = false, verbose = false, cigar = false, check = false, stage_times = false;
     const char* span_str = NULL;
     const char* pen2_str = NULL;
+    const char* wfad_str = NULL;
 
 
     int c;
@@ -113,6 +117,7 @@ int main(int argc, char** argv) {
             case 1000: stage_times = true; break;      /* (not in the reference: the library's stage clocks of the call on stderr) */
             case 1001: span_str = optarg; break;       /* (not in the reference: WFA2's ends-free alignment) */
             case 1002: pen2_str = optarg; break;       /* (not in the reference: WFA2's gap_affine_2p) */
+            case 1003: wfad_str = optarg; break;       /* (not in the reference: WFA2's wf-adaptive heuristic) */
             case 'h': usage(argv[0]); exit(0);
             default: break;      /* an option the tool does not know is skipped, like the reference's parser does (utils/arg_handler.c:97-140) */
         }
@@ -162,6 +167,26 @@ int main(int argc, char** argv) {
         if (wfagpu_amd_configure_affine2p(&pen2) != 0) return 1;
         LOG_INFO("Two-piece gap-affine penalties: M=0, X=%d, O1=%d, E1=%d, O2=%d, E2=%d.", pen2.mismatch, pen2.gap_opening1, pen2.gap_extension1,
                  pen2.gap_opening2, pen2.gap_extension2)
+    }
+    /* --wfa-adaptive: three integers, nothing behind them; not together with -B, --ends-free or --affine2p.  Checked before any
+     * device work, like those. */
+    if (wfad_str) {
+        wfagpu_amd_wfadaptive_t h = {0, 0, 0};
+        char tail = 0;
+        if (sscanf(wfad_str, "%d,%d,%d%c", &h.min_wavefront_length, &h.max_distance_threshold, &h.steps_between_cutoffs, &tail) != 3 ||
+            h.min_wavefront_length < 1 || h.max_distance_threshold < 0 || h.steps_between_cutoffs < 1) {
+            LOG_ERROR("--wfa-adaptive takes three integers min_len>=1,max_dist>=0,steps>=1 (got \"%s\").", wfad_str)
+            usage(argv[0]);
+            return 1;
+        }
+        if (band_arg != -2 || span_str || pen2_str) {
+            LOG_ERROR("--wfa-adaptive is a heuristic of the end-to-end gap-affine search: it is not combined with -B, --ends-free or --affine2p.")
+            usage(argv[0]);
+            return 1;
+        }
+        if (wfagpu_amd_configure_wfadaptive(&h) != 0) return 1;
+        LOG_INFO("WFA-Adaptive heuristic: min_wavefront_length=%d, max_distance_threshold=%d, steps_between_cutoffs=%d.", h.min_wavefront_length,
+                 h.max_distance_threshold, h.steps_between_cutoffs)
     }
     int x = 2, o = 3, e = 1;
     if (pen2_str) { x = pen2.mismatch; o = pen2.gap_opening1; e = pen2.gap_extension1; }      /* (sizes the default -e below; the library ignores them) */

@@ -370,3 +370,8 @@ int verification_cpu_score_2p_scratch(const char* pattern, const char* text, siz
     }
     return s;
 }
+
+int verification_heuristic_verdict(int distance, int optimum) {
+    if (distance < optimum) return -1;
+    return distance - optimum;
+}

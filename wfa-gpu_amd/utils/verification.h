@@ -59,6 +59,11 @@ int verification_cpu_score_2p_scratch(const char* pattern, const char* text, siz
 int verification_cpu_score_2p(const char* pattern, const char* text, size_t plen, size_t tlen,
                               int x, int o1, int e1, int o2, int e2);
 
+/* Under a heuristic (wfagpu_amd_wfadaptive_t; include/wfa_gpu_device.h) the CIGAR is checked as always -- it replays, its cost
+ * is the score -- but the score may lie above the optimum.  The verdict on a score against the CPU scorer's optimum: 0 equal,
+ * > 0 the excess of a score above the optimum (counted and said by -c, no failure), -1 a score BELOW the optimum (a failure). */
+int verification_heuristic_verdict(int distance, int optimum);
+
 #ifdef __cplusplus
 }
 #endif
