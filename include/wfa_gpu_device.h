@@ -168,7 +168,8 @@ int wfagpu_amd_prime(wfagpu_amd_ctx_t* ctx);
 void wfagpu_amd_debug_times(const wfagpu_amd_ctx_t* ctx, const void** d_records, unsigned int* records, int* waves);
 /* Diagnostics: which of the code objects that only some callers load this process has entered so far (launched, queried or
  * primed a kernel of) -- bit 0: the ends-free wavefront kernels, bit 1: the two-piece wavefront kernels, bit 2: the two-piece
- * backtrace kernels, bit 3: the wf-adaptive wavefront kernels.  Process-wide, never cleared.  A gap-affine end-to-end caller reads 0. */
+ * backtrace kernels, bit 3: the wf-adaptive wavefront kernels, bit 4: the one-component (edit, indel, gap-linear) wavefront kernels,
+ * bit 5: their backtrace kernels.  Process-wide, never cleared.  A gap-affine end-to-end caller reads 0. */
 unsigned int wfagpu_amd_debug_code_objects(void);
 
 /* The HIP stream (hipStream_t) the context runs on -- its own, or the one given at creation. */
@@ -272,6 +273,26 @@ int wfagpu_amd_align_device_adaptive(wfagpu_amd_ctx_t* ctx, const wfagpu_amd_bat
  * that is asked for is not used (said once on stderr).  NULL: the exact search again.  A bad member (as above), or a span or
  * two-piece penalties are configured: rejected (-1, message), state unchanged -- as are those while a heuristic is configured. */
 int wfagpu_amd_configure_wfadaptive(const wfagpu_amd_wfadaptive_t* heuristic);
+
+/* Edit, indel and gap-linear distances: WFA2's distance metrics with ONE wavefront component (the values are WFA2's
+ * distance_metric_t).  Match 0, mismatch `mismatch` > 0, every gap base `indel` > 0 -- both read under GAP_LINEAR only; EDIT is
+ * (1, 1); INDEL is indel = 1 with no mismatch move at all (its CIGARs never hold an X).  Scores and CIGARs are WFA2's, byte for
+ * byte.  End to end, exact (no band, no span, no second piece, no heuristic). */
+typedef enum { WFAGPU_AMD_METRIC_INDEL = 0, WFAGPU_AMD_METRIC_EDIT = 1, WFAGPU_AMD_METRIC_GAP_LINEAR = 2 } wfagpu_amd_metric_t;
+typedef struct { int metric, mismatch, indel; } wfagpu_amd_linear_t;
+
+/* wfagpu_amd_align_device under such a metric, on kernels of its own (one component per score: a third of the cells and a ring of
+ * max(mismatch, indel) + 1 rows).  max_error is the score budget as there.  linear == NULL, an unknown metric, or GAP_LINEAR with a
+ * member <= 0: -1. */
+int wfagpu_amd_align_device_linear(wfagpu_amd_ctx_t* ctx, const wfagpu_amd_batch_t* batch, const wfagpu_amd_linear_t* linear, int max_error,
+                                   bool compute_cigar, int32_t* d_scores, const char** d_text, const unsigned long long** d_off,
+                                   const unsigned int** d_len);
+
+/* Process-wide, like wfagpu_amd_configure_span: launch_alignments*, wfagpu_align and the CLI align under this metric; the
+ * affine_penalties_t they are handed is ignored and a band that is asked for is not used (each said once on stderr).  NULL: gap-affine
+ * again.  A bad member (as above), or a span, two-piece penalties or the wf-adaptive heuristic are configured: rejected (-1, message),
+ * state unchanged -- as are those while a metric is configured. */
+int wfagpu_amd_configure_linear(const wfagpu_amd_linear_t* linear);
 
 void wfagpu_amd_last_stats(const wfagpu_amd_ctx_t* ctx, wfagpu_amd_stats_t* out);
 

@@ -1,0 +1,296 @@
+"""Edit, indel and gap-linear distances on the GPU: wfagpu_amd_align_device_linear, wfagpu_amd_configure_linear behind the
+launch_alignments* seam and the CLI, against WFA2's scores and CIGARs (tests/golden/linear.*, made by
+tests/golden/make_golden_linear.py; the sets are described in tests/linear_ref.py)."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import linear_ref as lr
+import oracle_lib
+import wfagpu
+
+pytestmark = pytest.mark.gpu
+PKG = os.path.dirname(wfagpu.LIB_PATH)
+CLI = os.path.join(PKG, "bin", "wfa.affine.gpu")
+# score budgets of the first tier: above every golden score of the set (small: 472, small_edit: 276, ties: 12, lanes: 464, wide: 2400)
+MAX_ERROR = {"small": 600, "small_edit": 400, "ties": 100, "lanes": 700, "wide": 3000}
+
+
+@pytest.fixture(scope="module")
+def sets():
+    return {name: lr.read_golden(name) for name in lr.SETS + (lr.LONG_SET,)}
+
+
+def _run_set(al, g, cigar, max_error, only=None):
+    """Every metric group of a golden set as one call -> scores, cigars in the set's order (only: a subset of indices).  No pair is
+    skipped: every index must have come back."""
+    n = len(g["pairs"])
+    scores = np.full(n, -12345, dtype=np.int64)
+    cigars = [None] * n
+    seen = 0
+    stats = []
+    for metric, idx in lr.groups(g).items():
+        if only is not None:
+            idx = [i for i in idx if i in only]
+            if not idx:
+                continue
+        buf, meta = wfagpu.layout_pairs([g["pairs"][i] for i in idx])
+        batch = al.upload(buf, meta)
+        s, c = al.align(batch, None, max_error=max_error, compute_cigar=cigar, linear=metric)
+        stats.append(al.stats())
+        for j, i in enumerate(idx):
+            scores[i] = s[j]
+            cigars[i] = c[j] if cigar else None
+        seen += len(idx)
+    assert seen == (n if only is None else len(only))
+    return scores, cigars, stats
+
+
+def _check_set(g, scores, cigars, cigar, only=None):
+    for i in (range(len(g["pairs"])) if only is None else sorted(only)):
+        p, t = g["pairs"][i]
+        metric = g["metrics"][i]
+        where = (i, len(p), len(t), metric)
+        assert scores[i] == g["scores"][i], where
+        if cigar:
+            assert cigars[i] == g["cigars"][i], where
+            ok, cost = lr.check_cigar_linear(p, t, cigars[i], metric)
+            assert ok and cost == scores[i], where + (cigars[i],)
+
+
+@pytest.mark.parametrize("name", lr.SETS)
+@pytest.mark.parametrize("cigar", [False, True])
+@pytest.mark.parametrize("careful_only", [0, 1])
+def test_golden_sets(sets, name, cigar, careful_only):
+    """score == WFA2's, CIGAR == WFA2's byte for byte, valid, and its cost under the metric is the score -- as shipped and with
+    tuning.careful_only (every score on the careful step).  The one-component kernels have the careful loop only so far (DESIGN.md
+    section 4.9), so both settings run the same code; the parametrisation is what a lean loop has to pass when it comes."""
+    g = sets[name]
+    al = wfagpu.DeviceAligner(0, careful_only=careful_only)
+    try:
+        scores, cigars, _ = _run_set(al, g, cigar, MAX_ERROR[name])
+        _check_set(g, scores, cigars, cigar)
+    finally:
+        al.close()
+
+
+@pytest.mark.parametrize("variant", ["min_tier1", "min_tier2", "min_tier3", "max_error8", "small_arena", "trace_mode1", "trace_mode2",
+                                     "trace_mode3", "trace_mode4"])
+def test_ties_and_lanes_on_every_path(sets, variant):
+    """The same batches forced through the wider tiers, through escalation (a budget of 8: every pair of lanes holds a planted indel of
+    63 bases or more and misses it), through several arena-bound passes, and through every mapping of the backtrace: the same bytes.
+    (A metric group of lanes is six pairs, which one MiB of arena holds: the small arena also takes small_edit, 400 pairs in one call
+    whose 200 unrelated pairs of score ~150-270 leave about half their score squared in origin bytes each -- several MiB.)"""
+    kw, max_error = {}, None
+    if variant.startswith("min_tier"):
+        kw["min_tier"] = int(variant[-1])
+    elif variant.startswith("trace_mode"):
+        kw["trace_mode"] = int(variant[-1])
+    elif variant == "max_error8":
+        max_error = 8
+    elif variant == "small_arena":
+        kw["arena_bytes"] = 1 << 20      # (a fixed arena of 1 MiB: small_edit does not fit it at once)
+    al = wfagpu.DeviceAligner(0, **kw)
+    try:
+        passes = retried = 0
+        for name in ("ties", "lanes") + (("small_edit",) if variant == "small_arena" else ()):
+            g = sets[name]
+            scores, cigars, stats = _run_set(al, g, True, max_error or MAX_ERROR[name])
+            _check_set(g, scores, cigars, True)
+            passes = max(passes, max(st.sub_batches for st in stats))
+            retried += sum(st.pairs_retried for st in stats)
+            if variant.startswith("min_tier"):
+                t = int(variant[-1])
+                assert all(sum(st.pairs_tier[:t]) == 0 for st in stats)
+        if variant == "max_error8":
+            assert retried >= len(sets["lanes"]["pairs"])
+        if variant == "small_arena":
+            assert passes > 1
+    finally:
+        al.close()
+
+
+def test_one_wave_tier_and_byte_compare_class(sets):
+    """ties fits the one-wave tier; the pairs of small with N / IUPAC bytes run in the byte-compare kernels (WFA2 compares bytes as they
+    are)."""
+    al = wfagpu.DeviceAligner(0)
+    try:
+        g = sets["ties"]
+        scores, cigars, stats = _run_set(al, g, True, MAX_ERROR["ties"])
+        _check_set(g, scores, cigars, True)
+        assert sum(st.pairs_tier[0] for st in stats) == len(g["pairs"])
+        g = sets["small"]
+        only = {i for i, (p, t) in enumerate(g["pairs"]) if set(p + t) - set(b"ACGT")}
+        assert len(only) >= 8
+        for cigar in (False, True):
+            scores, cigars, stats = _run_set(al, g, cigar, MAX_ERROR["small"], only=only)
+            _check_set(g, scores, cigars, cigar, only=only)
+            assert sum(st.pairs_raw for st in stats) == len(only)
+    finally:
+        al.close()
+
+
+def test_sequences_beyond_16_bit_offsets(sets):
+    """33.5 kbp pairs: the tier whose ring holds 32-bit offsets in global memory."""
+    g = sets[lr.LONG_SET]
+    al = wfagpu.DeviceAligner(0)
+    try:
+        for cigar in (False, True):
+            scores, cigars, stats = _run_set(al, g, cigar, 3000)
+            _check_set(g, scores, cigars, cigar)
+            assert sum(st.pairs_tier[3] for st in stats) == len(g["pairs"])
+    finally:
+        al.close()
+
+
+def test_the_metrics_against_gap_affine_with_a_zero_opening(golden_dir):
+    """On the reference's 1 kbp pairs: linear=("linear", x, g) against wfagpu_amd_align_device under (x, 0, g), ("edit",) against (1, 0, 1),
+    on the same context.  Scores always; CIGAR bytes because WFA2 agrees with itself there (tests/test_linear_cpu.py,
+    test_wfa2_agrees_with_its_gap_affine_self_at_a_zero_opening; linear_ref.SEQ1K_CIGARS_AGREE)."""
+    pairs = wfagpu.read_seq_file(os.path.join(golden_dir, "seq1k.seq"))
+    buf, meta = wfagpu.layout_pairs(pairs)
+    al = wfagpu.DeviceAligner(0)
+    try:
+        batch = al.upload(buf, meta)
+        for metric, pen in lr.SEQ1K_CROSS:
+            s0, c0 = al.align(batch, pen, max_error=1000, compute_cigar=True)
+            s1, c1 = al.align(batch, None, max_error=1000, compute_cigar=True, linear=metric)
+            assert np.array_equal(s1, s0), metric
+            if lr.SEQ1K_CIGARS_AGREE:
+                assert c1 == c0, metric
+            s2, _ = al.align(batch, None, max_error=1000, compute_cigar=False, linear=metric)
+            assert np.array_equal(s2, s0), metric
+    finally:
+        al.close()
+
+
+def test_big_batch():
+    """8192 pairs of ~150 bases under edit in one call (where a gap-affine call would draw a sample for score budgets): the scores of
+    the same pairs in batches of 512, and of the dynamic program on a seeded sample of 256."""
+    rng = lr.Rng(20260304)
+    pairs = []
+    for i in range(8192):
+        p = rng.seq(rng.integer(120, 181))
+        pairs.append((p, rng.mutate(p, 0.06) if i % 4 else rng.seq(rng.integer(120, 181))))
+    al = wfagpu.DeviceAligner(0)
+    try:
+        buf, meta = wfagpu.layout_pairs(pairs)
+        batch = al.upload(buf, meta)
+        s_all, _ = al.align(batch, None, max_error=200, compute_cigar=False, linear=lr.EDIT)
+        assert al.stats().auto_budget == 0      # (no budgets from a sample under these metrics)
+        parts = []
+        for lo in range(0, len(pairs), 512):
+            buf, meta = wfagpu.layout_pairs(pairs[lo:lo + 512])
+            batch = al.upload(buf, meta)
+            parts.append(al.align(batch, None, max_error=200, compute_cigar=False, linear=lr.EDIT)[0])
+        assert np.array_equal(s_all, np.concatenate(parts))
+        for i in (lr.Rng(7).u64(256) % np.uint64(len(pairs))).astype(np.int64):
+            assert s_all[i] == lr.dp_linear_score(pairs[i][0], pairs[i][1], 1, 1), i
+    finally:
+        al.close()
+
+
+def _launch(pairs, pen, cigar, max_error, batch_size, band=-1, band_width=0):
+    lib = wfagpu.load()
+    buf, meta = wfagpu.layout_pairs(pairs)
+    n = len(pairs)
+    res = C.POINTER(wfagpu.AlignmentResult)()
+    assert lib.initialize_wfa_results(C.byref(res), n, 256 if cigar else 1)
+    opt = wfagpu.Options(max_error=max_error, threads_per_block=band_width, num_workers=1, band=band, batch_size=batch_size,
+                         num_alignments=n, penalties=wfagpu.Penalties(*pen), compute_cigar=cigar)
+    fn = lib.launch_alignments if cigar else lib.launch_alignments_distance
+    fn(buf.ctypes.data, buf.nbytes, meta.ctypes.data, res, opt, False)
+    scores = np.array([res[i].error for i in range(n)], dtype=np.int64)
+    cigars = [C.string_at(res[i].cigar.buffer).decode() for i in range(n)] if cigar else None
+    lib.destroy_wfa_results(res, n)
+    return scores, cigars
+
+
+def test_a_configured_metric_behind_the_launch_seam(sets):
+    """wfagpu_amd_configure_linear: launch_alignments and launch_alignments_distance on two device slots with a batch size that cuts
+    the call, the gap-affine penalties of the options ignored; a band that is asked for gives the exact results; after configure(NULL)
+    the very same call gives the gap-affine (2,3,1) answers of the oracle again."""
+    g = sets["small_edit"]
+    buf, meta = wfagpu.layout_pairs(g["pairs"])
+    ga_scores, ga_cigars, _ = oracle_lib.oracle_batch(buf, meta, (2, 3, 1), cigar=True)
+    assert not np.array_equal(ga_scores, g["scores"])      # (the two models do differ on these pairs)
+    try:
+        wfagpu.configure_launch(virtual_devices=2)
+        wfagpu.configure_linear(lr.EDIT)
+        s, c = _launch(g["pairs"], (2, 3, 1), True, 400, 37)
+        assert np.array_equal(s, g["scores"]) and c == g["cigars"]
+        s, _ = _launch(g["pairs"], (2, 3, 1), False, 400, 37)
+        assert np.array_equal(s, g["scores"])
+        s, c = _launch(g["pairs"], (2, 3, 1), True, 400, 150, band=25, band_width=64)
+        assert np.array_equal(s, g["scores"]) and c == g["cigars"]
+        wfagpu.configure_linear()
+        s, c = _launch(g["pairs"], (2, 3, 1), True, 800, 37)
+        assert np.array_equal(s, ga_scores) and c == list(ga_cigars)
+        s, _ = _launch(g["pairs"], (2, 3, 1), False, 800, 37)
+        assert np.array_equal(s, ga_scores)
+    finally:
+        wfagpu.configure_linear()
+
+
+def test_cli_edit_and_indel(sets, tmp_path):
+    """--edit with -x -c -o on small_edit written as a .seq file: the output file is the golden .alg byte for byte, and the -c
+    verification (the CIGAR priced under the metric, the score against the one-table CPU program) finds nothing wrong.  A .seq file
+    cannot carry an empty sequence: the two pairs of the set that have one are left out of the input, and their two lines out of the
+    golden bytes.  --indel on the same file: verified the same way, and no X anywhere in the output."""
+    g = sets["small_edit"]
+    seq = tmp_path / "nonempty.seq"
+    keep = [i for i, (p, t) in enumerate(g["pairs"]) if p and t]
+    assert len(keep) == len(g["pairs"]) - 2
+    with open(seq, "wb") as f:
+        for i in keep:
+            f.write(b">" + g["pairs"][i][0] + b"\n<" + g["pairs"][i][1] + b"\n")
+    out = tmp_path / "res.out"
+    r = subprocess.run([CLI, "-i", str(seq), "--edit", "-e", "400", "-x", "-c", "-b", "150", "-o", str(out)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "Incorrect=0" in r.stderr and all(tok == "Incorrect=0" for tok in r.stderr.split() if tok.startswith("Incorrect="))
+    golden_lines = open(lr.golden_path("small_edit"), "rb").read().splitlines(keepends=True)
+    assert open(out, "rb").read() == b"".join(golden_lines[i] for i in keep)
+    out2 = tmp_path / "res.indel.out"
+    r = subprocess.run([CLI, "-i", str(seq), "--indel", "-e", "700", "-x", "-c", "-b", "150", "-o", str(out2)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "Incorrect=0" in r.stderr and all(tok == "Incorrect=0" for tok in r.stderr.split() if tok.startswith("Incorrect="))
+    lines = open(out2, "rb").read().splitlines()
+    assert len(lines) == len(keep) and all(b"X" not in line for line in lines)
+
+
+_FRESH_PROCESS = r"""
+import sys
+import numpy as np
+import wfagpu
+lib = wfagpu.load()
+buf, meta = wfagpu.generate_pairs(64, 300, 0.05, seed=11)
+al = wfagpu.DeviceAligner(0)
+assert lib.wfagpu_amd_prime(al.ctx) == 0
+batch = al.upload(buf, meta)
+for cigar in (False, True):
+    al.align(batch, (2, 3, 1), max_error=100, compute_cigar=cigar)
+    al.align(batch, (4, 6, 2), max_error=200, compute_cigar=cigar, band=25, band_width=64)
+    al.align(batch, None, max_error=400, compute_cigar=cigar, affine2p=(4, 6, 2, 24, 1))
+    al.align(batch, (4, 6, 2), max_error=400, compute_cigar=cigar, wfadaptive=(10, 50, 1))
+print("others", lib.wfagpu_amd_debug_code_objects() & 48)
+al.align(batch, None, max_error=100, compute_cigar=False, linear=("edit",))
+print("edit scores", lib.wfagpu_amd_debug_code_objects() & 48)
+al.align(batch, None, max_error=100, compute_cigar=True, linear=("edit",))
+print("edit cigars", lib.wfagpu_amd_debug_code_objects() & 48)
+al.close()
+"""
+
+
+def test_other_calls_never_load_the_one_component_code_objects():
+    """A fresh process: wfagpu_amd_prime with nothing configured and gap-affine, banded, two-piece and wf-adaptive calls (with and
+    without CIGARs) enter neither of the one-component code objects (wfagpu_amd_debug_code_objects, bits 4 and 5); a score-only edit
+    call enters the wavefront unit (bit 4) alone, one with CIGARs the backtrace unit (bit 5) too."""
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.dirname(os.path.abspath(wfagpu.__file__)), os.environ.get("PYTHONPATH", "")]))
+    r = subprocess.run([sys.executable, "-c", _FRESH_PROCESS], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    seen = dict(line.rsplit(" ", 1) for line in r.stdout.splitlines() if line[:4] in ("othe", "edit"))
+    assert seen == {"others": "0", "edit scores": "16", "edit cigars": "48"}, r.stdout

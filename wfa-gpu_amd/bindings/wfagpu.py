@@ -91,6 +91,25 @@ class WfAdaptive(C.Structure):  # wfagpu_amd_wfadaptive_t: WFA2's wf-adaptive he
     _fields_ = [("min_wavefront_length", C.c_int), ("max_distance_threshold", C.c_int), ("steps_between_cutoffs", C.c_int)]
 
 
+class Linear(C.Structure):  # wfagpu_amd_linear_t: an edit, indel or gap-linear metric (one wavefront component)
+    _fields_ = [("metric", C.c_int), ("mismatch", C.c_int), ("indel", C.c_int)]
+
+
+METRIC_INDEL, METRIC_EDIT, METRIC_GAP_LINEAR = 0, 1, 2      # wfagpu_amd_metric_t (WFA2's distance_metric_t)
+
+
+def _as_linear(linear):
+    """("edit",) | ("indel",) | ("linear", x, g) -> Linear"""
+    name = linear[0]
+    if name == "edit" and len(linear) == 1:
+        return Linear(METRIC_EDIT, 0, 0)
+    if name == "indel" and len(linear) == 1:
+        return Linear(METRIC_INDEL, 0, 0)
+    if name == "linear" and len(linear) == 3:
+        return Linear(METRIC_GAP_LINEAR, int(linear[1]), int(linear[2]))
+    raise ValueError(f"a metric is ('edit',), ('indel',) or ('linear', x, g), not {tuple(linear)}")
+
+
 class Stats(C.Structure):  # wfagpu_amd_stats_t
     _fields_ = [("pack_ms", C.c_float), ("align_ms", C.c_float), ("trace_ms", C.c_float), ("total_ms", C.c_float),
                 ("align_launches", C.c_int), ("cells", C.c_ulonglong), ("arena_units", C.c_ulonglong),
@@ -118,6 +137,7 @@ ABI_SYMBOLS = [
     "wfagpu_amd_align_device_span", "wfagpu_amd_configure_span",
     "wfagpu_amd_align_device_2p", "wfagpu_amd_configure_affine2p", "wfagpu_amd_debug_code_objects",
     "wfagpu_amd_align_device_adaptive", "wfagpu_amd_configure_wfadaptive",
+    "wfagpu_amd_align_device_linear", "wfagpu_amd_configure_linear",
 ]
 
 _lib = None
@@ -166,6 +186,11 @@ def load():
     lib.wfagpu_amd_align_device_adaptive.restype = C.c_int
     lib.wfagpu_amd_configure_wfadaptive.argtypes = [C.POINTER(WfAdaptive)]
     lib.wfagpu_amd_configure_wfadaptive.restype = C.c_int
+    lib.wfagpu_amd_align_device_linear.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Linear), C.c_int, C.c_bool, C.c_void_p,
+                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.wfagpu_amd_align_device_linear.restype = C.c_int
+    lib.wfagpu_amd_configure_linear.argtypes = [C.POINTER(Linear)]
+    lib.wfagpu_amd_configure_linear.restype = C.c_int
     lib.wfagpu_amd_debug_code_objects.argtypes = []
     lib.wfagpu_amd_debug_code_objects.restype = C.c_uint
     lib.wfagpu_amd_last_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
@@ -263,6 +288,18 @@ def configure_wfadaptive(heuristic=None):
         return
     if lib.wfagpu_amd_configure_wfadaptive(C.byref(WfAdaptive(*[int(v) for v in heuristic]))) != 0:
         raise ValueError(f"wfagpu_amd_configure_wfadaptive rejected {tuple(heuristic)}")
+
+
+def configure_linear(linear=None):
+    """wfagpu_amd_configure_linear: launch_alignments*, wfagpu_align and the CLI align under an edit, indel or gap-linear metric --
+    ("edit",), ("indel",) or ("linear", x, g) --; the gap-affine penalties they are handed are ignored.  None: gap-affine again.  Raises
+    ValueError when the library rejects it (a bad member, or a span, two-piece penalties or the heuristic are configured)."""
+    lib = load()
+    if linear is None:
+        lib.wfagpu_amd_configure_linear(None)
+        return
+    if lib.wfagpu_amd_configure_linear(C.byref(_as_linear(linear))) != 0:
+        raise ValueError(f"wfagpu_amd_configure_linear rejected {tuple(linear)}")
 
 
 def last_launch_stats():
@@ -523,7 +560,7 @@ class DeviceAligner:
         return d_packed.cpu().numpy().view(np.uint32), d_flags.cpu().numpy()
 
     def align(self, batch, penalties, max_error, compute_cigar, band=-1, band_width=0, fetch=True, d_scores=None, span=None,
-              fetch_ends=False, affine2p=None, wfadaptive=None):
+              fetch_ends=False, affine2p=None, wfadaptive=None, linear=None):
         """Returns (scores ndarray, cigars list or None).  With fetch=False results stay on the device
         and (d_scores tensor, (text_ptr, off_ptr, len_ptr)) is returned.  d_scores: the caller's int32 device tensor for the scores
         (the C interface takes the caller's buffer: a loop of calls need not allocate one per call).
@@ -533,7 +570,9 @@ class DeviceAligner:
         affine2p: (x, o1, e1, o2, e2), two-piece gap-affine penalties (wfagpu_amd_align_device_2p; exact end-to-end search: a band or a
         span is an error); `penalties` is ignored then.
         wfadaptive: (min_wavefront_length, max_distance_threshold, steps_between_cutoffs), WFA2's wf-adaptive heuristic
-        (wfagpu_amd_align_device_adaptive; end to end, gap-affine: a band, a span or two pieces is an error)."""
+        (wfagpu_amd_align_device_adaptive; end to end, gap-affine: a band, a span or two pieces is an error).
+        linear: ("edit",), ("indel",) or ("linear", x, g), an edit, indel or gap-linear metric (wfagpu_amd_align_device_linear; exact
+        end-to-end search on one-component kernels: a band, a span, two pieces or the heuristic is an error); `penalties` is ignored then."""
         torch = self.torch
         dev = torch.device("cuda", self.device)
         n = batch.num_pairs
@@ -541,12 +580,14 @@ class DeviceAligner:
             d_scores = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         assert d_scores.dtype == torch.int32 and d_scores.numel() >= max(n, 1) and d_scores.is_cuda
         t, o, l = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        pen = Penalties(*penalties) if affine2p is None else Penalties(0, 0, 0)
+        pen = Penalties(*penalties) if (affine2p is None and linear is None) else Penalties(0, 0, 0)
         span = _as_span(span)
         if affine2p is not None and (span is not None or (band > 0 and band_width > 0)):
             raise ValueError("two-piece penalties are not combined with an ends-free span or the adaptive band")
         if wfadaptive is not None and (span is not None or affine2p is not None or (band > 0 and band_width > 0)):
             raise ValueError("the wf-adaptive heuristic is not combined with an ends-free span, two-piece penalties or the adaptive band")
+        if linear is not None and (span is not None or affine2p is not None or wfadaptive is not None or (band > 0 and band_width > 0)):
+            raise ValueError("an edit, indel or gap-linear metric is not combined with a span, two-piece penalties, the heuristic or the adaptive band")
         d_ends = None
         if span is not None:
             if band > 0 and band_width > 0:
@@ -556,7 +597,10 @@ class DeviceAligner:
         elif fetch_ends:
             raise ValueError("fetch_ends needs a span")
         self._inputs_ready()
-        if wfadaptive is not None:
+        if linear is not None:
+            rc = self.lib.wfagpu_amd_align_device_linear(self.ctx, C.byref(batch), C.byref(_as_linear(linear)), int(max_error),
+                                                         bool(compute_cigar), d_scores.data_ptr(), C.byref(t), C.byref(o), C.byref(l))
+        elif wfadaptive is not None:
             rc = self.lib.wfagpu_amd_align_device_adaptive(self.ctx, C.byref(batch), pen, int(max_error), C.byref(WfAdaptive(*[int(v) for v in wfadaptive])),
                                                            bool(compute_cigar), d_scores.data_ptr(), C.byref(t), C.byref(o), C.byref(l))
         elif affine2p is not None:
@@ -571,7 +615,7 @@ class DeviceAligner:
                                                   bool(compute_cigar), d_scores.data_ptr(), C.byref(t), C.byref(o),
                                                   C.byref(l))
         if rc != 0:
-            raise RuntimeError(f"wfagpu_amd_align_device{'_adaptive' if wfadaptive is not None else '_2p' if affine2p is not None else '_span' if span is not None else ''} failed ({rc})")
+            raise RuntimeError(f"wfagpu_amd_align_device{'_linear' if linear is not None else '_adaptive' if wfadaptive is not None else '_2p' if affine2p is not None else '_span' if span is not None else ''} failed ({rc})")
         if not fetch:
             res = (d_scores[:n], (t.value, o.value, l.value))
             return res + (d_ends[:n],) if fetch_ends else res

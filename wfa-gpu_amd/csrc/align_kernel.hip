@@ -66,6 +66,7 @@
 //   align/loop_careful.inc    the careful score step (WFA2 to the letter)
 //   align/loop_careful_2p.inc the careful score step of the two-piece instantiations
 //   align/loop_careful_ad.inc the careful score step of the wf-adaptive instantiations (WFA2's heuristic cut-off)
+//   align/loop_careful_lin.inc the careful score step of the one-component instantiations (edit, indel, gap-linear), cells included
 //   align/band_window.inc, align/loop_banded.inc   the adaptive band: the reference's window rule, the banded search
 #include <type_traits>
 
@@ -206,14 +207,20 @@ __device__ __forceinline__ ColdParams cold_params() {
 // (wavefront_heuristic.c:508-561).  A heuristic's rows depend on every cell WFA2 computes, so neither the window nor the reach
 // interval prunes: a row is bounded by the sequences and by the ring (|k| <= (s - o) / e up to score s), M carries WFA2's trimmed
 // limits; a score step of its own (align/loop_careful_ad.inc), origin bytes in ROWS.
+// LINEAR (align_kernel_lin.hip includes this file for those instantiations): WFA2's edit, indel and gap_linear distances -- mismatch x,
+// every gap base g (carried as e = oe = g), no mismatch move under indel (x == WFA_LIN_NO_MISMATCH: a kernel argument, wave-uniform).  One component per score: a
+// ring of max(x, g) + 1 rows of M and nothing else (de == 0), no run-limit row, I / D entries of the row book never set; a score step
+// of its own with its cells (align/loop_careful_lin.inc: the careful one, WFA2 to the letter), origin bytes BTL_* in ROWS.  Window
+// and reach: below, where they are derived.
 template <int NW, bool BT, typename OffT, bool GLOBAL_RING, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool TIMED = false, bool ENDSFREE = false,
-          bool TWOPIECE = false, bool ADAPTIVE = false>
+          bool TWOPIECE = false, bool ADAPTIVE = false, bool LINEAR = false>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu((NW == 1 && !BANDED) ? WPE : 1, 8)))
 wfa_align_kernel(const WfaAlignParams p) {
   static_assert(!HYBRID || (!GLOBAL_RING && !BANDED), "the hybrid ring is an exact LDS tier");
   static_assert(!ENDSFREE || (!BANDED && !HYBRID && !TIMED), "ends-free: the exact search of tiers 0, 1, 2 and 3");
   static_assert(!TWOPIECE || (!BANDED && !HYBRID && !TIMED && !ENDSFREE), "two pieces: the end-to-end exact search of tiers 0, 1, 2 and 3");
   static_assert(!ADAPTIVE || (!BANDED && !HYBRID && !TIMED && !ENDSFREE && !TWOPIECE), "wf-adaptive: end to end, gap-affine, tiers 0, 1, 2 and 3");
+  static_assert(!LINEAR || (!BANDED && !HYBRID && !TIMED && !ENDSFREE && !TWOPIECE && !ADAPTIVE), "one component: the end-to-end exact search of tiers 0, 1, 2 and 3");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NT = NW * 64;
   const int tid = threadIdx.x;
@@ -234,13 +241,13 @@ wfa_align_kernel(const WfaAlignParams p) {
   // read lands in a row's cells or in its guard zones (GZ columns on either side, NULL) and needs no range test; after a
   // re-centring jump the generic cells range-check every read.
   constexpr bool HOT = !GLOBAL_RING && sizeof(OffT) == 2;
-  constexpr bool HM_ROW = HOT && !HYBRID && NW == 1 && !BANDED;
+  constexpr bool HM_ROW = HOT && !HYBRID && NW == 1 && !BANDED && !LINEAR;
   // TILED (round 6): the origin bytes of the one-wave exact tier go into a block of TILES that the alignment owns as a whole --
   // 64-byte tiles of 4 scores x 16 diagonals, tile (s >> 2, (k - wlo) >> 4) at a fixed pitch, byte (s & 3) * 16 + ((k - wlo) & 15) -- instead
   // of one bump-allocated row per score behind a row table (wfa_device.h).  The backward walk of a 1 kbp alignment then touches ~35
   // cache lines instead of 74 (55 origin bytes on 55 lines + 19 lines of row table: wfa_walk_kernel is bound by random 64-byte
   // accesses), and a score of the lean loops neither sizes, claims nor records a row: no refill test, no row-table entry.
-  constexpr bool TILED = BT && HOT && !HYBRID && NW == 1 && !BANDED && !ENDSFREE && !TWOPIECE && !ADAPTIVE;      // (ends-free, two pieces, wf-adaptive: ROWS in every tier)
+  constexpr bool TILED = BT && HOT && !HYBRID && NW == 1 && !BANDED && !ENDSFREE && !TWOPIECE && !ADAPTIVE && !LINEAR;      // (ends-free, two pieces, wf-adaptive, one component: ROWS in every tier)
   const int GZ = BANDED ? 4 * dm + 2 : 0;
   const int x = p.x, oe = p.oe, e = p.e;
   // (TWOPIECE) the second piece; ring rows in all: dm of M, de each of I1 and D1, de2 each of I2 and D2
@@ -362,6 +369,8 @@ wfa_align_kernel(const WfaAlignParams p) {
       // up at least one base of the plen + tlen there are -- a gap base one, for at most o + e; a mismatch two, for x -- so no answer
       // costs more than max(x, o + e) (plen + tlen).  It bounds the row table.)
       if constexpr (ADAPTIVE) worst = (long long)max(x, oe) * ((long long)plen + tlen);
+      // (LINEAR: a mismatch, or an insertion and a deletion where those cost less -- always so under indel, whose x is out of reach)
+      if constexpr (LINEAR) worst = (long long)min(x, 2 * e) * min(plen, tlen) + (long long)e * abs(kend);
       budget = (int)min((long long)budget, worst);
     }
     int wlo = -plen, whi = tlen;
@@ -371,6 +380,16 @@ wfa_align_kernel(const WfaAlignParams p) {
       // base), so a ring of that many diagonals on either side of 0 holds every row up to the budget; the score step checks it.
       const long long kmax = budget >= oe ? ((long long)budget - (oe - e)) / e : 0;
       wlo = -(int)min((long long)plen, kmax); whi = (int)min((long long)tlen, kmax);
+    } else if constexpr (LINEAR) {
+      // One component, every gap base g.  A path moves by one diagonal per gap base, so one that visits a diagonal t beyond both 0 and
+      // kend holds at least t + (t + |kend|) gap bases: g (2 t + |kend|) <= S.  The window is (S / g - |kend|) / 2 diagonals on either
+      // side of [min(0, kend), max(0, kend)]; feasible: g |kend| <= S.  (Mismatches stay on their diagonal: the same under indel.)
+      if (budget < INT_MAX / 2) {
+        const int ak = kend < 0 ? -kend : kend, gb = budget / e;
+        feasible = ak <= gb;
+        const int t = feasible ? (gb - ak) / 2 : 0;
+        whi = min(max(0, kend) + t, tlen); wlo = max(min(0, kend) - t, -plen);
+      }
     } else if constexpr (TWOPIECE) {
       // Two pieces.  A gap of n bases costs g(n) = min(o1 + n e1, o2 + n e2), and g is subadditive (wfa_device.h), so a path that visits a
       // diagonal t beyond both 0 and kend holds gaps of at least t + |kend| bases in one direction and t in the other:
@@ -616,7 +635,8 @@ wfa_align_kernel(const WfaAlignParams p) {
       // the D row that belongs to an I row (same slot of the other ring)
       OffT* const d_first = HYBRID ? Dg + kidx0 : i_first + de * rs;
       auto d_of = [&](OffT* ip) -> OffT* { return d_first + (ip - i_first); };
-      OffT* p_m = m_first; OffT* p_x = m_first + (dm - x) * rs; OffT* p_oe = m_first + (dm - oe) * rs;
+      // (LINEAR under indel: x names no row, the pointer stays inside the ring and is never read through)
+      OffT* p_m = m_first; OffT* p_x = m_first + (dm - (LINEAR ? min(x, dm) : x)) * rs; OffT* p_oe = m_first + (dm - oe) * rs;
       OffT* p_ic = i_first; OffT* p_ip = i_first + (de - e) * rs;
       // (TWOPIECE) the I2 ring behind the D ring, the D2 ring behind it; the M row of s-(o2+e2), the I2 rows of s and s-e2; and the rows
       // of the second piece that cells_of_score reads and writes (set by the score step in front of every call)
@@ -636,6 +656,7 @@ wfa_align_kernel(const WfaAlignParams p) {
       // reaches the end |k - kend| bases away for no less than |k - kend| min(e1, e2) -- by going on in its piece, or by closing and
       // opening the other one.  g(|k - kend|) would be the bound for M cells alone: under (4,6,2,24,1) and a budget of 20 the gap of five
       // insertions to kend = 5 (cost 16) passes I1[8][1], four diagonals from the end with 12 left, where g(4) = 14.
+      // (LINEAR: a cell of score s on diagonal k is |k - kend| gap bases from the end: g |k - kend| <= budget - s, the same interval with e = g)
       const int e_reach = TWOPIECE ? min(e, e2) : e;
       const bool bounded = budget < INT_MAX / 2;
       int reach_r = bounded ? budget % e_reach : INT_MAX;
@@ -693,6 +714,8 @@ wfa_align_kernel(const WfaAlignParams p) {
           #include "align/loop_careful_2p.inc"
         } else if constexpr (ADAPTIVE) {
           #include "align/loop_careful_ad.inc"
+        } else if constexpr (LINEAR) {
+          #include "align/loop_careful_lin.inc"
         } else {
           #include "align/loop_banded.inc"
           #include "align/loop_lean_e1.inc"
@@ -729,9 +752,9 @@ wfa_align_kernel(const WfaAlignParams p) {
 }
 
 template <int NW, bool BT, typename OffT, bool GR, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool TIMED = false, bool EF = false, bool TP = false,
-          bool AD = false>
+          bool AD = false, bool LIN = false>
 void launch_inst(const WfaAlignParams& p, size_t lds, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
-  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE, TIMED, EF, TP, AD>;
+  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE, TIMED, EF, TP, AD, LIN>;
   // the opt-in for large dynamic LDS is sticky per device and per kernel: pay the driver call once
   static thread_local size_t allowed[16] = {0};
   int dev = 0;
@@ -743,9 +766,9 @@ void launch_inst(const WfaAlignParams& p, size_t lds, int grid, hipStream_t stre
   wfa_launch_timed(k, dim3(grid), dim3(NW * 64), lds, stream, ev0, ev1, p);
 }
 
-template <int NW, bool BT, typename OffT, bool GR, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool EF = false, bool TP = false, bool AD = false>
+template <int NW, bool BT, typename OffT, bool GR, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool EF = false, bool TP = false, bool AD = false, bool LIN = false>
 int occ_inst(size_t lds) {
-  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE, false, EF, TP, AD>;
+  auto k = wfa_align_kernel<NW, BT, OffT, GR, RAW, BANDED, HYBRID, WPE, false, EF, TP, AD, LIN>;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   int nb = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), NW * 64, lds) != hipSuccess) {
@@ -755,7 +778,49 @@ int occ_inst(size_t lds) {
   return nb;
 }
 
-#if defined(WFA_ALIGN_ADAPTIVE_UNIT)
+#if defined(WFA_ALIGN_LINEAR_UNIT)
+// ---- the one-component translation unit (align_kernel_lin.hip): tiers 0, 1, 2 and 3, with and without backtrace, packed and byte-compare
+template <bool BT, bool RAW>
+void launch_tier_lin(const WfaAlignParams& p, int tier, size_t lds, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  switch (tier) {
+    case 0: launch_inst<1, BT, int16_t, false, RAW, false, false, 8, false, false, false, false, true>(p, lds, grid, stream, ev0, ev1); break;
+    case 1: launch_inst<4, BT, int16_t, false, RAW, false, false, 8, false, false, false, false, true>(p, lds, grid, stream, ev0, ev1); break;
+    case 2: launch_inst<16, BT, int16_t, false, RAW, false, false, 8, false, false, false, false, true>(p, lds, grid, stream, ev0, ev1); break;
+    default:
+      if (p.ring16) launch_inst<16, BT, int16_t, true, RAW, false, false, 8, false, false, false, false, true>(p, lds, grid, stream, ev0, ev1);
+      else launch_inst<16, BT, int32_t, true, RAW, false, false, 8, false, false, false, false, true>(p, lds, grid, stream, ev0, ev1);
+      break;
+  }
+}
+template <bool BT, bool RAW>
+int occ_tier_lin(int tier, size_t lds) {
+  switch (tier) {
+    case 0: return occ_inst<1, BT, int16_t, false, RAW, false, false, 8, false, false, false, true>(lds);
+    case 1: return occ_inst<4, BT, int16_t, false, RAW, false, false, 8, false, false, false, true>(lds);
+    case 2: return occ_inst<16, BT, int16_t, false, RAW, false, false, 8, false, false, false, true>(lds);
+    default: return occ_inst<16, BT, int32_t, true, RAW, false, false, 8, false, false, false, true>(lds);
+  }
+}
+
+}  // namespace
+
+void wfa_launch_align_lin(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  wfa_unit_entered(WFA_UNIT_ALIGN_LIN);
+  const size_t lds = wfa_align_lds_bytes(p, tier);
+  if (with_bt) { if (raw) launch_tier_lin<true, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_lin<true, false>(p, tier, lds, grid, stream, ev0, ev1); }
+  else { if (raw) launch_tier_lin<false, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_lin<false, false>(p, tier, lds, grid, stream, ev0, ev1); }
+}
+
+int wfa_align_lin_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds) {
+  wfa_unit_entered(WFA_UNIT_ALIGN_LIN);
+  if (with_bt) return raw ? occ_tier_lin<true, true>(tier, lds) : occ_tier_lin<true, false>(tier, lds);
+  return raw ? occ_tier_lin<false, true>(tier, lds) : occ_tier_lin<false, false>(tier, lds);
+}
+
+// (this code object is loaded by the first launch of one of its kernels: wfagpu_amd_prime does that only under a configured metric)
+namespace { __global__ void k_prime_align_lin() {} }
+void wfa_prime_align_lin(hipStream_t stream) { wfa_unit_entered(WFA_UNIT_ALIGN_LIN); hipLaunchKernelGGL(k_prime_align_lin, dim3(1), dim3(64), 0, stream); }
+#elif defined(WFA_ALIGN_ADAPTIVE_UNIT)
 // ---- the wf-adaptive translation unit (align_kernel_ad.hip): tiers 0, 1, 2 and 3, with and without backtrace, packed and byte-compare
 template <bool BT, bool RAW>
 void launch_tier_ad(const WfaAlignParams& p, int tier, size_t lds, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
@@ -955,7 +1020,7 @@ int occ_tier_banded(int tier, size_t lds) {
 size_t wfa_align_lds_bytes(const WfaAlignParams& p, int tier) {
   size_t ring = 0;
   if (tier == 4) ring = (((size_t)(p.dm + p.de) * p.rs * sizeof(int16_t)) + 15) & ~(size_t)15;       // hybrid: M and I rings
-  else if (tier != 3) ring = (((size_t)(p.dm + 2 * p.de + 2 * p.de2 + ((tier == 0 && p.band_width <= 0) ? 1 : 0)) * p.rs * sizeof(int16_t)) + 15) & ~(size_t)15;     // (+ the run-limit row of the one-wave exact kernels)
+  else if (tier != 3) ring = (((size_t)(p.dm + 2 * p.de + 2 * p.de2 + ((tier == 0 && p.band_width <= 0 && p.de > 0) ? 1 : 0)) * p.rs * sizeof(int16_t)) + 15) & ~(size_t)15;     // (+ the run-limit row of the one-wave exact kernels; not the one-component ones)
   const size_t seq = (size_t)2 * p.seq_words_cap * 4;
   // reduction slots [24] + broadcast [2] + (NW > 1) row book [3][book]
   const size_t bk = (size_t)p.book_mask + 1;

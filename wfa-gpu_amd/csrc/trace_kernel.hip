@@ -315,8 +315,18 @@ constexpr uint32_t OP_NONE = 0;
 // o2 + e2 (wavefront_backtrace.c:354-415).  In M the byte names the component the offset came from; inside a gap component its flag
 // says whether the extension won, or tied, against the opening.  The operations stay X / I / D.
 // (one walk step per translation unit: the unit macro selects its body)
+// One component (WFA_TRACE_LINEAR_UNIT, trace_kernel_lin.hip, origin bytes BTL_*): the walk never leaves M -- score steps x and g
+// (carried as p.e), a run of matches may follow every operation (wavefront_backtrace.c:254-302).  On a border (v or h zero) the only
+// valid source is the gap along it, so the walk arrives at (0, 0) through the run WFA2 prints there (:275, 311-313).
 __device__ __forceinline__ uint32_t walk_step(const uint32_t code, int& state, int& s, int& k, const WfaTraceParams& p) {
-#ifdef WFA_TRACE_TWOPIECE_UNIT
+#if defined(WFA_TRACE_LINEAR_UNIT)
+  const uint32_t org = code & BTL_MASK;
+  if (org == BTL_NONE) return OP_NONE;
+  const bool is_x = org == BTL_X, is_d = org == BTL_D;
+  s -= is_x ? p.x : p.e;
+  k += is_x ? 0 : (is_d ? 1 : -1);
+  return (is_x ? OP_X : (is_d ? OP_D : OP_I)) | OP_EXT_AFTER;
+#elif defined(WFA_TRACE_TWOPIECE_UNIT)
   uint32_t after = 0;
   int st = state;
   if (st == 0) {
@@ -1073,7 +1083,10 @@ void launch_wave(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0, hi
 
 // ev0 / ev1: receive the start of the first and the end of the last kernel launched here (a call that launches nothing --
 // n_work == 0 -- leaves them alone: returns false)
-#ifdef WFA_TRACE_TWOPIECE_UNIT
+#if defined(WFA_TRACE_LINEAR_UNIT)
+bool wfa_launch_trace_lin(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  wfa_unit_entered(WFA_UNIT_TRACE_LIN);
+#elif defined(WFA_TRACE_TWOPIECE_UNIT)
 bool wfa_launch_trace_2p(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
   wfa_unit_entered(WFA_UNIT_TRACE_2P);
 #else
@@ -1132,7 +1145,11 @@ bool wfa_launch_trace(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev
 
 // Loads this translation unit's code object on the current device (the runtime loads a code object at the first launch of
 // any of its kernels: 5-25 ms each): launch_alignments* call it while a cold call waits for its first upload.
-#ifdef WFA_TRACE_TWOPIECE_UNIT
+#if defined(WFA_TRACE_LINEAR_UNIT)
+// (this code object is loaded by the first launch of one of its kernels: wfagpu_amd_prime does that only under a configured metric)
+namespace { __global__ void k_prime_trace_lin() {} }
+void wfa_prime_trace_lin(hipStream_t stream) { wfa_unit_entered(WFA_UNIT_TRACE_LIN); hipLaunchKernelGGL(k_prime_trace_lin, dim3(1), dim3(64), 0, stream); }
+#elif defined(WFA_TRACE_TWOPIECE_UNIT)
 // (this code object is loaded by the first launch of one of its kernels: wfagpu_amd_prime does that only under configured two-piece penalties)
 namespace { __global__ void k_prime_trace_2p() {} }
 void wfa_prime_trace_2p(hipStream_t stream) { wfa_unit_entered(WFA_UNIT_TRACE_2P); hipLaunchKernelGGL(k_prime_trace_2p, dim3(1), dim3(64), 0, stream); }

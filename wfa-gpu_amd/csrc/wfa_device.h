@@ -59,6 +59,10 @@ enum : uint32_t { BT_M_NONE = 0, BT_M_X = 12, BT_M_D = 8, BT_M_I = 4, BT_M_MASK 
 enum : uint32_t { BT2_M_NONE = 0, BT2_M_X = 5u << 4, BT2_M_D2 = 4u << 4, BT2_M_D1 = 3u << 4, BT2_M_I2 = 2u << 4, BT2_M_I1 = 1u << 4, BT2_M_MASK = 7u << 4,
                   BT2_D2_EXT = 8, BT2_I2_EXT = 4, BT2_D1_EXT = 2, BT2_I1_EXT = 1 };
 
+// Edit, indel and gap-linear distances (the LINEAR instantiations, align_kernel_lin.hip): one component, 2 bits used -- the source of M,
+// by WFA2's priority on equal offsets (wavefront_backtrace.c:49-59, 259-264: mismatch, deletion, insertion; never a mismatch under indel)
+enum : uint32_t { BTL_NONE = 0, BTL_X = 3, BTL_D = 2, BTL_I = 1, BTL_MASK = 3 };
+
 // Two-piece gap cost and what a budget affords (host and device).  A gap of n bases costs g(n) = min(o1 + n e1, o2 + n e2), g(0) = 0;
 // g is increasing, concave and subadditive (g(a) + g(b) >= g(a + b)): several gaps never cost less than one gap of their bases.
 // (oe1 = o1 + e1, oe2 = o2 + e2, as the kernels carry them)
@@ -166,7 +170,11 @@ struct WfaAlignParams {
   // wf-adaptive (only the ADAPTIVE instantiations, align_kernel_ad.hip, read these; ad_steps == 0: exact search): WFA2's
   // min_wavefront_length, max_distance_threshold, steps_between_cutoffs
   int ad_min_len, ad_max_dist, ad_steps;
+  // (edit, indel and gap-linear distances -- the LINEAR instantiations, align_kernel_lin.hip -- add no field: mismatch x, every gap base e,
+  // oe == e, de == 0 -- no I / D rows, which is how the host tells these calls apart --, dm = max(x, e) + 1 rows of M; indel, which has no
+  // mismatch move, is x = WFA_LIN_NO_MISMATCH with dm = e + 1)
 };
+constexpr int WFA_LIN_NO_MISMATCH = 1 << 30;
 
 struct WfaTraceParams {
   int raw;                       // 1: sequences are the ASCII buffer (byte compare), 0: 2-bit packed
@@ -217,6 +225,7 @@ struct WfaTraceParams {
   int32_t* ends;
   int extra_items;               // RLE items a text may have beyond 2 * operations + 1 (the two free runs): sizes the upper-bound text slots
   int oe2, e2;                   // two-piece gap-affine (wfa_launch_trace_2p only): the second piece; origin bytes are BT2_*
+  // (wfa_launch_trace_lin: oe == e is the cost of a gap base, origin bytes are BTL_*)
 };
 
 // Host-side launchers (one per translation unit).
@@ -276,10 +285,25 @@ void wfa_prime_align_ad(hipStream_t stream);
 // launch_alignments* -- wants its wfagpu_amd_align_device call to run under (nullptr: exact), as three ints.
 bool wfa_configured_wfadaptive(int* out3);
 const int* wfa_lane_wfadaptive3();
+// The one-component instantiations (align_kernel_lin.hip: a code object of their own, loaded only by calls under an edit, indel or
+// gap-linear metric): tiers 0, 1, 2 and 3, exact search, careful loop, origin bytes in ROWS.  wfa_align_lds_bytes serves them too
+// (WfaAlignParams::de == 0).
+void wfa_launch_align_lin(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream,
+                          hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+int wfa_align_lin_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds_bytes);
+void wfa_prime_align_lin(hipStream_t stream);
+// The metric of wfagpu_amd_configure_linear (wfa_launch.hip): false when none is configured; out (optional) receives
+// {metric, mismatch, indel}.  wfa_lane_linear3: what the calling thread -- a lane of launch_alignments* -- wants its
+// wfagpu_amd_align_device call to run under (nullptr: gap-affine), as three ints.
+bool wfa_configured_linear(int* out3);
+const int* wfa_lane_linear3();
 bool wfa_launch_trace(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);     // false: nothing to launch
 // (the backtrace of two-piece alignments: trace_kernel_2p.hip, the same kernels compiled for five walk states and BT2_* origin bytes)
 bool wfa_launch_trace_2p(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 void wfa_prime_trace_2p(hipStream_t stream);
+// (the backtrace of edit, indel and gap-linear alignments: trace_kernel_lin.hip, the same kernels compiled for one walk state and BTL_* origin bytes)
+bool wfa_launch_trace_lin(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+void wfa_prime_trace_lin(hipStream_t stream);
 // Tier 5 (short_kernel.hip): 64 / lanes alignments per wavefront (lanes = 16 or 32 diagonals each), rings in registers; with_bt: one row
 // of `lanes` origin bytes per score for the backtrace.
 bool wfa_short_supported(int x, int oe, int e);
@@ -296,7 +320,7 @@ const WfaShortEntry* wfa_short_entry_e4(int ascii, int bt, int l32, int idx);
 // Which of the optional code objects -- the ones only some callers load -- this process has entered: every host function that launches,
 // queries or primes a kernel of such a unit says so (the runtime loads a code object at the first of these).  Process-wide, never
 // cleared; wfagpu_amd_debug_code_objects() (wfa_host.hip) hands the bits out, tests check "never loaded" with them.
-enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u, WFA_UNIT_ALIGN_AD = 8u };
+enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u, WFA_UNIT_ALIGN_AD = 8u, WFA_UNIT_ALIGN_LIN = 16u, WFA_UNIT_TRACE_LIN = 32u };
 void wfa_unit_entered(unsigned unit);
 // Code-object priming: one empty launch per kernel translation unit (see the definitions).
 void wfa_prime_pack(hipStream_t stream);

@@ -512,6 +512,7 @@ int wfagpu_amd_prime(wfagpu_amd_ctx_t* c) {
   if (wfa_configured_span(nullptr)) wfa_prime_align_ef(c->stream);      // (the ends-free kernels: only callers under a span load them)
   if (wfa_configured_affine2p(nullptr)) { wfa_prime_align_2p(c->stream); wfa_prime_trace_2p(c->stream); }  // (the two-piece kernels: only callers under such penalties)
   if (wfa_configured_wfadaptive(nullptr)) wfa_prime_align_ad(c->stream);      // (the wf-adaptive kernels: only callers under the heuristic)
+  if (wfa_configured_linear(nullptr)) { wfa_prime_align_lin(c->stream); wfa_prime_trace_lin(c->stream); }  // (the one-component kernels: only callers under such a metric)
   LAUNCH_K(k_iota, dim3(1), dim3(64), 0, c->stream, static_cast<uint32_t*>(nullptr), 0u, 0u);      // (this file's)
   HIP_TRY(hipGetLastError());
   c->primed = true;
@@ -610,7 +611,10 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   // comes back as a BAND failure and is escalated like any other.  Tiers 0, 1, 2 and 3 only.
   // Two pieces (p.e2 > 0): tiers 0, 1, 2 and 3 of the exact search, like ends-free; never combined with it.
   // wf-adaptive (p.ad_steps > 0): tiers 0, 1, 2 and 3 likewise, rings sized by window_width_ad; never combined with either.
-  const bool ef = p.ends != nullptr, tp2 = p.e2 > 0, ad = p.ad_steps > 0;
+  // One component (p.de == 0: edit, indel, gap-linear): tiers 0, 1, 2 and 3 likewise.  Its window -- (S / g - |kend|) / 2 diagonals on
+  // either side of the end diagonals -- is widest at |kend| = S / g: S / g + 1 diagonals, which is window_width with o = 0; its ring is
+  // dm rows and nothing else (de == 0), which wfa_align_lds_bytes sees: a pair that needs four waves under gap-affine may fit one here.
+  const bool ef = p.ends != nullptr, tp2 = p.e2 > 0, ad = p.ad_steps > 0, lin = p.de == 0;
   int width = ad ? window_width_ad(max_score, p.oe - p.e, p.e, max_seq_len) : tp2 ? window_width_2p(max_score, p, max_seq_len) : window_width(max_score, p.oe - p.e, p.e, max_seq_len);
   if (ef) {
     const long long m = max_seq_len;
@@ -620,7 +624,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   // Short wavefronts, score only (tier 5, short_kernel.hip): when the diagonal window of the budget fits 16 or 32 lanes, four or two
   // alignments share a wavefront and the rings live in registers (BASELINE configs[1]: 150 bp reads, budgets of ~14 once
   // they are tuned).  Pairs whose own window is wider (large |tlen - plen|) come back as BAND failures and go on as always.
-  if (!ef && !tp2 && !ad && !raw && !(p.ascii && !c->short_ascii_ok) && c->tuning.min_tier == 0 && !(bt && c->tuning.no_short_cigar) && wfa_short_supported(p.x, p.oe, p.e) && width + 1 <= 32 && max_score <= 30000) {
+  if (!ef && !tp2 && !ad && !lin && !raw && !(p.ascii && !c->short_ascii_ok) && c->tuning.min_tier == 0 && !(bt && c->tuning.no_short_cigar) && wfa_short_supported(p.x, p.oe, p.e) && width + 1 <= 32 && max_score <= 30000) {
     const int lanes = width + 1 <= 16 ? 16 : 32;
     p.rs = 0;
     const size_t lds = wfa_short_lds_bytes(p, lanes, bt);
@@ -648,13 +652,13 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     if (t == 0 && (width > 1024 || p.dm > 64)) continue;
     if (t == 1 && width > 8192) continue;
     if (t == 1 && few_pairs && width >= 1024 && !min_tier && wfa_align_lds_bytes(p, 2) <= budget[2]) continue;
-    int nb = ad ? wfa_align_ad_max_blocks_per_cu(t, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(t, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(t, bt, raw, lds) : wfa_align_max_blocks_per_cu(t, bt, raw, false, lds);
+    int nb = lin ? wfa_align_lin_max_blocks_per_cu(t, bt, raw, lds) : ad ? wfa_align_ad_max_blocks_per_cu(t, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(t, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(t, bt, raw, lds) : wfa_align_max_blocks_per_cu(t, bt, raw, false, lds);
     if (nb < 1) continue;
     // Occupancy-matched instantiation of the one-wave kernels: LDS decides how many rings a CU holds; compiled for 8 waves
     // per SIMD the kernel lives on 64 VGPRs and 78 SGPRs (123 scalar spills + scratch), which only pays when 8 waves per
     // SIMD really are resident.  The smallest of 4 / 6 / 7 / 8 that keeps all the rings LDS allows but at most one.
     int wpe = 8;
-    if (t == 0 && !raw && !ef && !tp2 && !ad) {
+    if (t == 0 && !raw && !ef && !tp2 && !ad && !lin) {
       const int forced = c->tuning.waves_per_simd;
       for (int w : {4, 6, 7, 8}) if (4 * w >= nb - 1) { wpe = w; break; }
       // (gap extensions > 1: the general lean loop carries more scalar state than the e == 1 loop; compiled for 8 waves per SIMD -- 64
@@ -672,7 +676,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     // (profiles/r02/mid_lengths.txt).  tuning.t0_min_blocks: A/B.
     const int t0_min_blocks = c->tuning.t0_min_blocks > 0 ? c->tuning.t0_min_blocks : 10;
     if (t == 0 && !min_tier && nb < t0_min_blocks && width >= 384) continue;
-    if (t == 1 && !raw && !ef && !tp2 && !ad && c->tuning.exact_two_waves) {
+    if (t == 1 && !raw && !ef && !tp2 && !ad && !lin && c->tuning.exact_two_waves) {
       // A/B hook: TWO waves per alignment where four would run (same ring, same LDS; half the per-score bookkeeping per chunk, half the waves)
       const size_t lds2 = wfa_align_lds_bytes(p, 6);
       const int nb2 = wfa_align_max_blocks_per_cu(6, bt, raw, false, lds2);
@@ -682,7 +686,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     return true;
   }
   // hybrid ring: everything but the D rows in LDS (one workgroup of 16 waves per CU)
-  if (i16_ok && !raw && !ef && !tp2 && !ad && min_tier != 3) {
+  if (i16_ok && !raw && !ef && !tp2 && !ad && !lin && min_tier != 3) {
     const size_t lds_h = wfa_align_lds_bytes(p, 4);
     if (lds_h <= c->lds_per_block_max) {
       const int nb = wfa_align_max_blocks_per_cu(4, bt, raw, false, lds_h);
@@ -692,7 +696,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   p.rs = rs_plain;
   const size_t lds = wfa_align_lds_bytes(p, 3);
   if (lds > c->lds_per_block_max) return false;   // sequences themselves do not fit LDS
-  const int nb = ad ? wfa_align_ad_max_blocks_per_cu(3, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(3, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(3, bt, raw, lds) : wfa_align_max_blocks_per_cu(3, bt, raw, false, lds);
+  const int nb = lin ? wfa_align_lin_max_blocks_per_cu(3, bt, raw, lds) : ad ? wfa_align_ad_max_blocks_per_cu(3, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(3, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(3, bt, raw, lds) : wfa_align_max_blocks_per_cu(3, bt, raw, false, lds);
   *out = {3, width, max_score, lds, std::max(1, std::min(nb, 2))};
   return true;
 }
@@ -724,8 +728,26 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
                              bool compute_cigar, int32_t* d_scores,
                              const char** d_text, const unsigned long long** d_off,
                              const unsigned int** d_len, const wfagpu_amd_span_t* span, int32_t* d_ends,
-                             const wfagpu_amd_penalties2p_t* pen2 = nullptr, const wfagpu_amd_wfadaptive_t* wfad = nullptr) {
+                             const wfagpu_amd_penalties2p_t* pen2 = nullptr, const wfagpu_amd_wfadaptive_t* wfad = nullptr,
+                             const wfagpu_amd_linear_t* linm = nullptr) {
   if (!c || !b || !d_scores) return -1;
+  // linm != nullptr: an edit, indel or gap-linear metric (align_kernel_lin.hip: one component), exact search, end to end; `pen` is ignored:
+  // it becomes (x, 0, g) -- a gap base costs g, nothing opens -- for everything below that only sizes or bounds; indel: x = 2 g, what an
+  // insertion and a deletion in place of a mismatch cost (the kernel gets ap.x = WFA_LIN_NO_MISMATCH: no mismatch move)
+  const bool lin = linm != nullptr;
+  if (lin) {
+    if (span || pen2 || wfad) { fprintf(stderr, "[!] ERROR: an edit, indel or gap-linear metric is not combined with a span, two-piece penalties or the wf-adaptive heuristic\n"); return -1; }
+    if (linm->metric == WFAGPU_AMD_METRIC_EDIT) { pen.x = 1; pen.e = 1; }
+    else if (linm->metric == WFAGPU_AMD_METRIC_INDEL) { pen.x = 2; pen.e = 1; }
+    else if (linm->metric == WFAGPU_AMD_METRIC_GAP_LINEAR && linm->mismatch > 0 && linm->indel > 0) { pen.x = linm->mismatch; pen.e = linm->indel; }
+    else {
+      fprintf(stderr, "[!] ERROR: a metric is indel (0), edit (1) or gap-linear (2) with mismatch > 0 and indel > 0 (got %d,%d,%d)\n", linm->metric, linm->mismatch, linm->indel);
+      return -1;
+    }
+    pen.o = 0;
+    band = -1; band_width = 0;
+  }
+  const bool lin_indel = lin && linm->metric == WFAGPU_AMD_METRIC_INDEL;
   const bool ef = span != nullptr;
   const bool tp2 = pen2 != nullptr;
   // wfad != nullptr: WFA2's wf-adaptive heuristic (align_kernel_ad.hip), end to end, gap-affine
@@ -831,6 +853,8 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
   ap.dm = std::max(pen.x, oe) + 1;
   ap.de = pen.e + 1;
   if (tp2) { ap.oe2 = o2 + e2; ap.e2 = e2; ap.de2 = e2 + 1; ap.dm = std::max(ap.dm, ap.oe2 + 1); }
+  // (one component: max(x, g) + 1 rows of M -- g + 1 under indel, whose x is only a bound -- and no I / D rows)
+  if (lin) { ap.de = 0; ap.dm = (lin_indel ? pen.e : std::max(pen.x, pen.e)) + 1; if (lin_indel) ap.x = WFA_LIN_NO_MISMATCH; }
   // (wf-adaptive under penalties reduced by their common factor: scores that are no multiple of it have no wavefront, and WFA2's
   // cut-off does not count those -- the same rows are cut)
   if (ad) { ap.ad_min_len = wfad->min_wavefront_length; ap.ad_max_dist = wfad->max_distance_threshold; ap.ad_steps = wfad->steps_between_cutoffs; }
@@ -860,7 +884,12 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
     if (w > 1024) return 0.0;      // (wider wavefronts run on the multi-wave tiers: rows behind a row table)
     return 64.0 * (double)((w + 15) / 16) * (double)(B / 4 + 1) + 512.0;
   };
-  if (ad) {
+  if (lin) {
+    // (one component: one byte per cell of the diamond -- rows behind a row table in every tier.  A row gains a diagonal on each side
+    // every g scores and the reach takes them back at the same rate: B^2 / (2 g) cells under a budget B)
+    const double B = std::min<unsigned>(max_error, 2 * max_len);
+    est_pair_bytes = 0.5 * (B + 1) * (B + 1) / pen.e + 16.0 * B + 4096.0;
+  } else if (ad) {
     // (wf-adaptive: rows behind a row table in every tier; nothing is pruned, so until the cut-off bites a row gains two diagonals
     // every e scores and loses none: B^2 / e bytes under a budget B -- an upper estimate, refined after every pass)
     const double B = std::min<unsigned>(max_error, 2 * max_len);
@@ -911,7 +940,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
   // 18 us + the gap between two launches of a 168 us step of 100k configs[1] pairs.  (ASCII dword indices are 32-bit there.)
   // (sequences_bytes may be missing from a caller's batch record: four times the packed words bound the ASCII layout from above)
   c->short_ascii_ok = std::max<size_t>(b->sequences_bytes, b->packed_bytes * 4) < ((size_t)1 << 34);
-  const bool short_fuses = !ef && !tp2 && !ad && wfa_short_supported(pen.x, oe, pen.e) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
+  const bool short_fuses = !ef && !tp2 && !ad && !lin && wfa_short_supported(pen.x, oe, pen.e) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
   const bool fused_pack = !prepacked && (b->max_seq_len >= 512u || short_fuses) && !c->tuning.no_fused_pack;
   // Every status starts as PENDING = 0: written by the pack kernel where it runs (it visits every pair anyway), by a memset (a
   // launch of its own, ~5 us + a gap) where it does not -- queued by whoever reads the array first (ensure_status), and not at all
@@ -1168,6 +1197,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
         else if (ef) wfa_launch_align_ef(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else if (tp2) wfa_launch_align_2p(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else if (ad) wfa_launch_align_ad(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
+        else if (lin) wfa_launch_align_lin(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else wfa_launch_align(ap, tp.tier, cigar_now, raw, grid, st, tp.wpe, L.e0, L.e1);
         {
           const hipError_t le = hipGetLastError();
@@ -1279,7 +1309,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
         tp.cigar_len = static_cast<uint32_t*>(c->cig_len[c->out_set].p);
         // (ev_t0 / ev_t1: start of the first and end of the last backtrace kernel)
         tp.walk_grid_cap = 2 * c->num_cus;      // (two workgroups = eight wavefronts per CU: trace_kernel.hip, wfa_walk_kernel)
-        traced = tp2 ? wfa_launch_trace_2p(tp, st, c->ev_t0, c->ev_t1) : wfa_launch_trace(tp, st, c->ev_t0, c->ev_t1);
+        traced = lin ? wfa_launch_trace_lin(tp, st, c->ev_t0, c->ev_t1) : tp2 ? wfa_launch_trace_2p(tp, st, c->ev_t0, c->ev_t1) : wfa_launch_trace(tp, st, c->ev_t0, c->ev_t1);
         HIP_TRY(hipGetLastError());
         // ---- pairs that ran out of arena go into the next pass (CIGAR calls only: score-only calls have no arena) ----
         // (none can where a tier-5 launch was the chain's only one and its slots fit the arena: the backtrace kernel is the chain's last
@@ -1416,7 +1446,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
       // (tuned budgets pay where they narrow a wide window -- or, score-only, where they bring it down to what the
       // several-alignments-per-wavefront tier holds)
       const bool short_ok = wfa_short_supported(pen.x, oe, pen.e) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar);
-      const bool would_tune = !ef && !tp2 && !ad && n >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) && (w_me > 128 || (w_me > 15 && short_ok));
+      const bool would_tune = !ef && !tp2 && !ad && !lin && n >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) && (w_me > 128 || (w_me > 15 && short_ok));
       bool inherited = false;
       if (would_tune && c->same_stream)
         for (int i = 0; i < c->n_saved_q; ++i) {
@@ -1464,7 +1494,8 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
       // (ends-free: no budgets from a sample -- the careful loop is the only one, and a read's score says little about a window's)
       // (two pieces: none either -- switched off, not tuned: DESIGN.md section 4.7)
       // (wf-adaptive: none either -- a budget from the exact scores of a sample says nothing about the heuristic's)
-      const bool try_budget = !ef && !tp2 && !ad && !raw && n_pending >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) &&
+      // (one component: none either)
+      const bool try_budget = !ef && !tp2 && !ad && !lin && !raw && n_pending >= 8192 && !c->tuning.no_auto_budget && !(want_band && c->tuning.force_band) &&
                               (w_me2 > 128 || (w_me2 > 15 && short_ok2));
       int saved_idx = -1;
       if (try_budget && c->same_stream) {
@@ -1635,6 +1666,12 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
     const wfagpu_amd_penalties2p_t p2{l2[0], l2[1], l2[2], l2[3], l2[4]};
     return align_device_impl(c, b, pen, max_error, band, band_width, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, &p2);
   }
+  // (and for a configured edit, indel or gap-linear metric: wfagpu_amd_configure_linear -- the penalties handed in are ignored)
+  const int* const ll = wfa_lane_linear3();
+  if (ll) {
+    const wfagpu_amd_linear_t lm{ll[0], ll[1], ll[2]};
+    return align_device_impl(c, b, affine_penalties_t{}, max_error, -1, 0, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, nullptr, nullptr, &lm);
+  }
   // (and for a configured wf-adaptive heuristic: wfagpu_amd_configure_wfadaptive)
   const int* const la = wfa_lane_wfadaptive3();
   if (la) {
@@ -1649,6 +1686,13 @@ extern "C" int wfagpu_amd_align_device_adaptive(wfagpu_amd_ctx_t* c, const wfagp
                                                 const char** d_text, const unsigned long long** d_off, const unsigned int** d_len) {
   // (NULL: the exact end-to-end search, whatever is configured for the lanes)
   return align_device_impl(c, b, pen, max_error, -1, 0, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, nullptr, heuristic);
+}
+
+extern "C" int wfagpu_amd_align_device_linear(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b, const wfagpu_amd_linear_t* linear, int max_error,
+                                              bool compute_cigar, int32_t* d_scores, const char** d_text, const unsigned long long** d_off,
+                                              const unsigned int** d_len) {
+  if (!linear) { fprintf(stderr, "[!] ERROR: wfagpu_amd_align_device_linear needs a metric\n"); return -1; }
+  return align_device_impl(c, b, affine_penalties_t{}, max_error, -1, 0, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, nullptr, nullptr, linear);
 }
 
 extern "C" int wfagpu_amd_align_device_2p(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b, const wfagpu_amd_penalties2p_t* pens, int max_error,

@@ -61,7 +61,36 @@ thread_local const int* t_lane_2p = nullptr;
 bool g_ad_set = false;
 int g_ad[3] = {0, 0, 0};
 thread_local const int* t_lane_ad = nullptr;
+// The process-wide edit, indel or gap-linear metric (wfagpu_amd_configure_linear), the same way (wfa_lane_linear3); under the same
+// mutex: never configured together with a span, two-piece penalties or the heuristic.
+bool g_lin_set = false;
+int g_lin[3] = {0, 0, 0};
+thread_local const int* t_lane_lin = nullptr;
 }  // namespace
+
+bool wfa_configured_linear(int* out3) {
+  std::lock_guard<std::mutex> lock(g_span_mutex);
+  if (out3 && g_lin_set) for (int i = 0; i < 3; ++i) out3[i] = g_lin[i];
+  return g_lin_set;
+}
+const int* wfa_lane_linear3() { return t_lane_lin; }
+
+extern "C" int wfagpu_amd_configure_linear(const wfagpu_amd_linear_t* m) {
+  if (m && !(m->metric == WFAGPU_AMD_METRIC_INDEL || m->metric == WFAGPU_AMD_METRIC_EDIT ||
+             (m->metric == WFAGPU_AMD_METRIC_GAP_LINEAR && m->mismatch > 0 && m->indel > 0))) {
+    fprintf(stderr, "[!] ERROR: a metric is indel (0), edit (1) or gap-linear (2) with mismatch > 0 and indel > 0 (got %d,%d,%d)\n", m->metric, m->mismatch, m->indel);
+    return -1;
+  }
+  std::lock_guard<std::mutex> lock(g_span_mutex);
+  if (m && (g_span_set || g_2p_set || g_ad_set)) {
+    fprintf(stderr, "[!] ERROR: an edit, indel or gap-linear metric is not combined with an ends-free span, two-piece penalties or the wf-adaptive heuristic (%s configured)\n",
+            g_span_set ? "a span is" : g_2p_set ? "such penalties are" : "it is");
+    return -1;
+  }
+  g_lin_set = m != nullptr;
+  if (m) { g_lin[0] = m->metric; g_lin[1] = m->mismatch; g_lin[2] = m->indel; }
+  return 0;
+}
 
 bool wfa_configured_wfadaptive(int* out3) {
   std::lock_guard<std::mutex> lock(g_span_mutex);
@@ -77,6 +106,10 @@ extern "C" int wfagpu_amd_configure_wfadaptive(const wfagpu_amd_wfadaptive_t* h)
     return -1;
   }
   std::lock_guard<std::mutex> lock(g_span_mutex);
+  if (h && g_lin_set) {
+    fprintf(stderr, "[!] ERROR: the wf-adaptive heuristic is not combined with an edit, indel or gap-linear metric (one is configured)\n");
+    return -1;
+  }
   if (h && (g_span_set || g_2p_set)) {
     fprintf(stderr, "[!] ERROR: the wf-adaptive heuristic is not combined with an ends-free span or two-piece penalties (%s configured)\n",
             g_span_set ? "a span is" : "they are");
@@ -111,6 +144,10 @@ extern "C" int wfagpu_amd_configure_affine2p(const wfagpu_amd_penalties2p_t* pen
     fprintf(stderr, "[!] ERROR: two-piece penalties are not combined with an ends-free span (one is configured)\n");
     return -1;
   }
+  if (pens && g_lin_set) {
+    fprintf(stderr, "[!] ERROR: two-piece penalties are not combined with an edit, indel or gap-linear metric (one is configured)\n");
+    return -1;
+  }
   if (pens && g_ad_set) {
     fprintf(stderr, "[!] ERROR: two-piece penalties are not combined with the wf-adaptive heuristic (it is configured)\n");
     return -1;
@@ -129,6 +166,10 @@ extern "C" int wfagpu_amd_configure_span(const wfagpu_amd_span_t* span) {
   std::lock_guard<std::mutex> lock(g_span_mutex);
   if (span && g_2p_set) {
     fprintf(stderr, "[!] ERROR: an ends-free span is not combined with two-piece penalties (they are configured)\n");
+    return -1;
+  }
+  if (span && g_lin_set) {
+    fprintf(stderr, "[!] ERROR: an ends-free span is not combined with an edit, indel or gap-linear metric (one is configured)\n");
     return -1;
   }
   if (span && g_ad_set) {
@@ -273,6 +314,10 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
   // (under a configured wf-adaptive heuristic: the CIGAR is valid and costs the score as always; the score may lie ABOVE the CPU
   // scorer's optimum -- such pairs are counted and said, they are no failures; a score below the optimum is one)
   const bool heuristic = wfa_configured_wfadaptive(nullptr);
+  // (under a configured edit, indel or gap-linear metric: the CIGAR priced under the metric -- an X under indel is a failure --, the
+  // score checked against the one-table program; the penalties of the options are not looked at)
+  int m3[3] = {0, 0, 0};
+  const int* const lm = wfa_configured_linear(m3) ? m3 : nullptr;
   std::atomic<long> above{0};
   std::atomic<long long> excess{0};
   auto worker = [&](unsigned) {
@@ -290,7 +335,8 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
         if (a.cigar) {
           const char* cg = a.results[i].cigar.buffer;
           const bool c1 = check_cigar_edit(text, pattern, m.text_len, m.pattern_len, cg);
-          const bool c2 = p2 ? check_affine2p_distance(text, pattern, m.text_len, m.pattern_len, dist, p2[0], p2[1], p2[2], p2[3], p2[4], cg)
+          const bool c2 = lm ? check_linear_distance(text, pattern, m.text_len, m.pattern_len, dist, lm[0], lm[1], lm[2], cg)
+                        : p2 ? check_affine2p_distance(text, pattern, m.text_len, m.pattern_len, dist, p2[0], p2[1], p2[2], p2[3], p2[4], cg)
                         : span ? check_affine_distance_span(text, pattern, m.text_len, m.pattern_len, dist, a.opt.penalties.x,
                                                             a.opt.penalties.o, a.opt.penalties.e, cg, span)
                                : check_affine_distance(text, pattern, m.text_len, m.pattern_len, dist, a.opt.penalties.x,
@@ -298,7 +344,8 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
           if (!c1) LOG_ERROR("Incorrect cigar (%ld). Distance: %d. CIGAR: %s", i, dist, cg);
           ok = c1 && c2;
         }
-        const int cpu = p2 ? verification_cpu_score_2p_scratch(pattern, text, m.pattern_len, m.text_len, p2[0], p2[1], p2[2], p2[3], p2[4], &scratch)
+        const int cpu = lm ? verification_cpu_score_linear(pattern, text, m.pattern_len, m.text_len, lm[0], lm[1], lm[2])
+                      : p2 ? verification_cpu_score_2p_scratch(pattern, text, m.pattern_len, m.text_len, p2[0], p2[1], p2[2], p2[3], p2[4], &scratch)
                       : span ? verification_cpu_score_span_scratch(pattern, text, m.pattern_len, m.text_len, a.opt.penalties.x,
                                                                    a.opt.penalties.o, a.opt.penalties.e, span, &scratch)
                              : verification_cpu_score_scratch(pattern, text, m.pattern_len, m.text_len, a.opt.penalties.x,
@@ -1017,11 +1064,22 @@ int run_device(const CallArgs& a, Shard& sh) {
         if (!warned3.exchange(true)) fprintf(stderr, "[!] WARNING: the adaptive band is not combined with the wf-adaptive heuristic: running under the heuristic alone\n");
       }
       t_lane_ad = under_ad ? h3 : nullptr;
+      // (and for a configured edit, indel or gap-linear metric -- wfagpu_amd_configure_linear --: the gap-affine penalties of the
+      // options are ignored and a band is not used, said once)
+      int m3[3];
+      const bool under_lin = wfa_configured_linear(m3);
+      if (under_lin) {
+        static std::atomic<bool> warned4{false};
+        if (!warned4.exchange(true)) fprintf(stderr, "[!] WARNING: a metric is configured (wfagpu_amd_configure_linear): the gap-affine penalties%s are ignored\n",
+                                             (a.opt.band > 0 && a.opt.threads_per_block > 0) ? " and the adaptive band" : "");
+      }
+      t_lane_lin = under_lin ? m3 : nullptr;
       const int arc = wfagpu_amd_align_device(L.ctx, &wb, a.opt.penalties, a.opt.max_error, a.opt.band, a.opt.threads_per_block, a.cigar,
                                               d_sc, &bo.d_text, &bo.d_off, &bo.d_len);
       t_lane_span = nullptr;
       t_lane_2p = nullptr;
       t_lane_ad = nullptr;
+      t_lane_lin = nullptr;
       if (arc) return arc;
       bo.d_scores = d_sc;
       if (a.cigar) { wfagpu_amd_stats_t stt; wfagpu_amd_last_stats(L.ctx, &stt); bo.text_bytes = stt.text_bytes; }

@@ -63,6 +63,10 @@ static void usage(const char* prog) {
            "\t                                  (WFA2's defaults: 4,6,2,24,1; exact search: not with -g, -B or --ends-free)\n"
            "\t    --wfa-adaptive <len,dist,steps> WFA2's wf-adaptive heuristic: min_wavefront_length, max_distance_threshold,\n"
            "\t                                  steps_between_cutoffs (WFA2's defaults: 10,50,1; not with -B, --ends-free or --affine2p)\n"
+           "\t    --edit                        Edit (Levenshtein) distance: mismatch 1, gap base 1, on one-component kernels\n"
+           "\t    --indel                       Indel (LCS) distance: gap base 1 and no mismatches (no X in a CIGAR)\n"
+           "\t    --gap-linear <x,g>            Gap-linear penalties: mismatch x, every gap base g\n"
+           "\t                                  (each of the three: not with another, -g, -B, --ends-free, --affine2p or --wfa-adaptive)\n"
            "[System]\n"
            "\t-t, --threads-per-block <int>     Accepted for compatibility (band width in banded mode)\n"
            "\t-w, --workers <int>               Accepted for compatibility\n"
@@ -86,13 +90,16 @@ int main(int argc, char** argv) {
         {"check", no_argument, 0, 'c'}, {"threads-per-block", required_argument, 0, 't'},
         {"workers", required_argument, 0, 'w'}, {"help", no_argument, 0, 'h'}, {"stage-times", no_argument, 0, 1000},
         {"ends-free", required_argument, 0, 1001}, {"affine2p", required_argument, 0, 1002},
-        {"wfa-adaptive", required_argument, 0, 1003}, {0, 0, 0, 0}};
+        {"wfa-adaptive", required_argument, 0, 1003}, {"edit", no_argument, 0, 1004}, {"indel", no_argument, 0, 1005},
+        {"gap-linear", required_argument, 0, 1006}, {0, 0, 0, 0}};
     const char *seq_path = NULL, *q_path = NULL, *t_path = NULL, *out_path = NULL, *pen_str = NULL;
     long n_read = 0, max_distance = -1, batch_size = -1, band_arg = -2, tpb = -1, workers = -1;
     bool print_out = false, verbose = false, cigar = false, check = false, stage_times = false;
     const char* span_str = NULL;
     const char* pen2_str = NULL;
     const char* wfad_str = NULL;
+    const char* lin_str = NULL;
+    int n_metric = 0, metric = -1;
 
 
     int c;
@@ -118,6 +125,9 @@ int main(int argc, char** argv) {
             case 1001: span_str = optarg; break;       /* (not in the reference: WFA2's ends-free alignment) */
             case 1002: pen2_str = optarg; break;       /* (not in the reference: WFA2's gap_affine_2p) */
             case 1003: wfad_str = optarg; break;       /* (not in the reference: WFA2's wf-adaptive heuristic) */
+            case 1004: metric = WFAGPU_AMD_METRIC_EDIT; ++n_metric; break;      /* (not in the reference: WFA2's edit, indel and gap_linear metrics) */
+            case 1005: metric = WFAGPU_AMD_METRIC_INDEL; ++n_metric; break;
+            case 1006: metric = WFAGPU_AMD_METRIC_GAP_LINEAR; lin_str = optarg; ++n_metric; break;
             case 'h': usage(argv[0]); exit(0);
             default: break;      /* an option the tool does not know is skipped, like the reference's parser does (utils/arg_handler.c:97-140) */
         }
@@ -188,7 +198,28 @@ int main(int argc, char** argv) {
         LOG_INFO("WFA-Adaptive heuristic: min_wavefront_length=%d, max_distance_threshold=%d, steps_between_cutoffs=%d.", h.min_wavefront_length,
                  h.max_distance_threshold, h.steps_between_cutoffs)
     }
+    /* --edit, --indel, --gap-linear x,g: one of them, not together with -g, -B, --ends-free, --affine2p or --wfa-adaptive.  Checked
+     * before any device work, like those. */
+    wfagpu_amd_linear_t lin = {0, 0, 0};
+    if (n_metric) {
+        lin.metric = metric;
+        if (n_metric > 1 || pen_str || band_arg != -2 || span_str || pen2_str || wfad_str) {
+            LOG_ERROR("--edit, --indel and --gap-linear are exact end-to-end searches under their own metric: not combined with each other, -g, -B, --ends-free, --affine2p or --wfa-adaptive.")
+            usage(argv[0]);
+            return 1;
+        }
+        char tail = 0;
+        if (lin_str && (sscanf(lin_str, "%d,%d%c", &lin.mismatch, &lin.indel, &tail) != 2 || lin.mismatch <= 0 || lin.indel <= 0)) {
+            LOG_ERROR("--gap-linear takes two positive integers x,g (got \"%s\").", lin_str)
+            usage(argv[0]);
+            return 1;
+        }
+        if (wfagpu_amd_configure_linear(&lin) != 0) return 1;
+        if (metric == WFAGPU_AMD_METRIC_GAP_LINEAR) LOG_INFO("Gap-linear penalties: M=0, X=%d, gap base %d.", lin.mismatch, lin.indel)
+        else LOG_INFO("%s distance.", metric == WFAGPU_AMD_METRIC_EDIT ? "Edit" : "Indel")
+    }
     int x = 2, o = 3, e = 1;
+    if (n_metric) { x = lin_str ? lin.mismatch : 1; o = 0; e = lin_str ? lin.indel : 1; }      /* (sizes the default -e below; the library ignores them) */
     if (pen2_str) { x = pen2.mismatch; o = pen2.gap_opening1; e = pen2.gap_extension1; }      /* (sizes the default -e below; the library ignores them) */
     if (pen_str && sscanf(pen_str, "%d,%d,%d", &x, &o, &e) != 3) {
         LOG_WARN("Invalid penalties format provided. Using default penalties (0,2,3,1).")

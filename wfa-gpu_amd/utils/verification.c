@@ -375,3 +375,62 @@ int verification_heuristic_verdict(int distance, int optimum) {
     if (distance < optimum) return -1;
     return distance - optimum;
 }
+
+/* Edit, indel and gap-linear distances (wfagpu_amd_linear_t): metric 0 indel, 1 edit, 2 gap-linear (x, g). */
+static bool linear_pens(int metric, int* x, int* g) {
+    if (metric == 1) { *x = 1; *g = 1; return true; }
+    if (metric == 0) { *x = 0; *g = 1; return true; }      /* (x = 0: no mismatch move) */
+    return metric == 2 && *x > 0 && *g > 0;
+}
+
+bool check_linear_distance(const char* text, const char* pattern, size_t tlen, size_t plen,
+                           int distance, int metric, int x, int g, const char* cigar) {
+    (void)text; (void)pattern; (void)tlen; (void)plen;
+    if (!linear_pens(metric, &x, &g)) return false;
+    long cost = 0;
+    const char* c = cigar;
+    while (*c) {
+        long n; char op;
+        c = next_item(c, &n, &op);
+        if (!c) return false;
+        if (op == 'X') { if (x == 0) return false; cost += n * x; }      /* (indel: an X is a failure) */
+        else if (op == 'I' || op == 'D') cost += n * g;
+        else if (op != 'M') return false;
+    }
+    return cost == distance;
+}
+
+/* Furthest-reaching points per (score, diagonal) in ONE table: a ring of max(x, g) + 1 rows over every diagonal of the pair, each
+ * row written whole (NONE outside the span of its score).  O(score * (plen + tlen)): a checker, plain on purpose. */
+int verification_cpu_score_linear(const char* pattern, const char* text, size_t plen_, size_t tlen_, int metric, int x, int g) {
+    if (!linear_pens(metric, &x, &g)) return -1;
+    const int plen = (int)plen_, tlen = (int)tlen_, kend = tlen - plen;
+    const int W = plen + tlen + 3, K0 = plen + 1, depth = (x > g ? x : g) + 1, NONE = -(1 << 29);
+    int* rows = (int*)malloc((size_t)depth * W * sizeof(int));
+    if (!rows) return -1;
+    for (long i = 0; i < (long)depth * W; ++i) rows[i] = NONE;
+    int h0 = 0;
+    while (h0 < plen && h0 < tlen && pattern[h0] == text[h0]) ++h0;
+    rows[K0] = h0;
+    int s = 0;
+    const long worst = (long)2 * g * (plen < tlen ? plen : tlen) + (long)g * (kend < 0 ? -kend : kend);
+    while (rows[(size_t)(s % depth) * W + K0 + kend] < tlen) {
+        ++s;
+        if (s > worst) { s = -1; break; }
+        int* cur = rows + (size_t)(s % depth) * W;
+        const int* rg = s >= g ? rows + (size_t)((s - g) % depth) * W : NULL;
+        const int* rx = (x > 0 && s >= x) ? rows + (size_t)((s - x) % depth) * W : NULL;
+        for (int k = -plen; k <= tlen; ++k) {
+            int best = NONE;
+            if (rx && rx[K0 + k] + 1 > best) best = rx[K0 + k] + 1;
+            if (rg && rg[K0 + k - 1] + 1 > best) best = rg[K0 + k - 1] + 1;
+            if (rg && rg[K0 + k + 1] > best) best = rg[K0 + k + 1];
+            int h = best, v = best - k;
+            if (h < 0 || v < 0 || h > tlen || v > plen) { cur[K0 + k] = NONE; continue; }
+            while (h < tlen && v < plen && pattern[v] == text[h]) { ++h; ++v; }
+            cur[K0 + k] = h;
+        }
+    }
+    free(rows);
+    return s;
+}

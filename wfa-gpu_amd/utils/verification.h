@@ -64,6 +64,13 @@ int verification_cpu_score_2p(const char* pattern, const char* text, size_t plen
  * > 0 the excess of a score above the optimum (counted and said by -c, no failure), -1 a score BELOW the optimum (a failure). */
 int verification_heuristic_verdict(int distance, int optimum);
 
+/* Edit, indel and gap-linear distances (wfagpu_amd_linear_t; include/wfa_gpu_device.h): metric 0 indel, 1 edit, 2 gap-linear with
+ * mismatch x and gap base g (x and g are read under gap-linear only).  The CIGAR is priced under the metric -- an X under indel is a
+ * failure --, the score checked against a one-table scalar program (-1: a bad metric, or no memory). */
+bool check_linear_distance(const char* text, const char* pattern, size_t tlen, size_t plen,
+                           int distance, int metric, int x, int g, const char* cigar);
+int verification_cpu_score_linear(const char* pattern, const char* text, size_t plen, size_t tlen, int metric, int x, int g);
+
 #ifdef __cplusplus
 }
 #endif
