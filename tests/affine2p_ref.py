@@ -10,13 +10,14 @@
 
 Penalties are (x, o1, e1, o2, e2): match 0, all five > 0."""
 import ctypes as C
+import math
 import os
 import struct
 
 import numpy as np
 
 import oracle_lib
-from endsfree_ref import Rng, parse_cigar
+from endsfree_ref import SWEEP_LONG, SWEEP_PAIRS, Rng, parse_cigar, sweep_long, sweep_pairs, sweep_top
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
@@ -201,10 +202,36 @@ def _plant(rng, s, n, insert):
     return s[:at] + rng.seq(n) + s[at:] if insert else s[:at] + s[at + n:]
 
 
+#   sweep          SWEEP_PAIRS short pairs (endsfree_ref.sweep_pairs) under each of SWEEP_PENS; SWEEP_LONG long pairs (sweep_long) under
+#                  each of SWEEP_LONG_PENS, M rings of 64 and 66 rows: either side of the one-wave tier's limit of 64.
+SWEEP_SET = "sweep"
+# two cheap sets; a common factor of 3; M rings of 64, 65 and 66 rows (max(x, o1 + e1, o2 + e2) + 1); a mismatch deeper than either piece; the
+# pieces swapped (the first is the flat one); a second piece that always wins (o2 < o1, e2 < e1); deep I/D rings (e1 = 6, e2 = 5);
+# e2 > e1 with o2 = o1 (the second piece never wins).  WFA2 accepts all eleven.
+SWEEP_PENS = ((1, 1, 2, 4, 1), (3, 2, 3, 9, 1), (6, 9, 3, 30, 3), (2, 3, 1, 62, 1), (2, 3, 1, 63, 1), (2, 3, 1, 64, 1), (40, 6, 2, 24, 1),
+              (4, 24, 1, 6, 2), (4, 6, 2, 3, 1), (5, 2, 6, 20, 5), (2, 1, 1, 1, 3))
+SWEEP_LONG_PENS = ((2, 3, 1, 62, 1), (2, 3, 1, 64, 1))
+
+
+def ring_depth(pen):
+    """Rows of the M ring the kernels run: one per score back to the deepest source, max(x, o1 + e1, o2 + e2) below, and the row being
+    written -- of the penalties without their common factor, which the library divides out first."""
+    x, o1, e1, o2, e2 = pen
+    return max(x, o1 + e1, o2 + e2) // math.gcd(*pen) + 1
+
+
 def make_set(name):
     """-> (pairs, pens) of a golden set."""
     pairs, pens = [], []
-    if name in ("small", ONE_PEN_SET):
+    if name == SWEEP_SET:
+        rng = Rng(20261002)
+        for j, pen in enumerate(SWEEP_PENS):
+            pairs += sweep_pairs(rng, sweep_top(ring_depth(pen)), j)
+            pens += [pen] * SWEEP_PAIRS
+        for pen in SWEEP_LONG_PENS:
+            pairs += sweep_long(rng)
+            pens += [pen] * SWEEP_LONG
+    elif name in ("small", ONE_PEN_SET):
         rng = Rng(20260201)
         for i in range(400):
             if i == 9:

@@ -9,6 +9,7 @@
 A span is (pattern_begin_free, pattern_end_free, text_begin_free, text_end_free); every value is clamped to the length of its sequence
 pair by pair (WFA2 rejects larger ones)."""
 import ctypes as C
+import math
 import os
 import re
 
@@ -231,10 +232,131 @@ class Rng:
         return bytes(out)
 
 
+# ---- the pairs of the `sweep` sets (shared with affine2p_ref, wfadaptive_ref and linear_ref) --------------------------------------
+# One parameter set of a sweep runs SWEEP_PAIRS short pairs; a budget equal to a pair's own score has to leave it on the one-wave tier,
+# whose ring is (ring depth + I/D rows) rows of (window + 2 * ring depth + a chunk of padding) 16-bit cells in 40 KiB.  So a set with a
+# deep ring (SWEEP_DEEP: depth >= 60, the ring alone is ~200 cells a row before the window) gets pairs of at most 48 bases and the others
+# pairs of at most 160, and unrelated pairs -- the largest scores -- are half as long as the rest.
+SWEEP_PAIRS, SWEEP_LONG, SWEEP_DEEP = 20, 5, 60
+
+
+def ring_depth(pen):
+    """Rows of the M ring the gap-affine kernels run under (x, o, e): one per score back to the deepest source, max(x, o + e) below, and
+    the row being written -- of the penalties without their common factor, which the library divides out first."""
+    return max(pen[0], pen[1] + pen[2]) // math.gcd(*pen) + 1
+
+
+def sweep_top(depth):
+    return 48 if depth >= SWEEP_DEEP else 160
+
+
+def sweep_pairs(rng, top, which, unrelated=None):
+    """SWEEP_PAIRS pairs of 0..top bases: 8 related at ~8 %, 4 unrelated, 4 with one planted gap of 1 to min(60, what fits) bases (the
+    first one base, the second the longest; the side that carries the gap alternates), 2 repeats of unequal length (a homopolymer, a
+    3-base tandem), 1 pair holding N (the byte-compare class), 1 pair with an empty side (the pattern where `which` is even)."""
+    pairs = []
+    for _ in range(8):
+        p = rng.seq(rng.integer(top // 4, top + 1))
+        pairs.append((p, rng.mutate(p, 0.08)[:top]))
+    for _ in range(4):
+        pairs.append((rng.seq(rng.integer(1, (unrelated or top // 2) + 1)), rng.seq(rng.integer(1, (unrelated or top // 2) + 1))))
+    for j in range(4):
+        base = rng.seq(rng.integer(3 * top // 8, 5 * top // 8 + 1))
+        room = min(60, top - len(base))
+        n = 1 if j == 0 else room if j == 1 else rng.integer(2, room)
+        at = rng.integer(1, len(base))
+        longer = base[:at] + rng.seq(n) + base[at:]
+        pairs.append((base, longer) if j % 2 == 0 else (longer, base))
+    for j in range(2):
+        unit = rng.seq(1 if j == 0 else 3)
+        left, right = rng.seq(rng.integer(4, top // 4)), rng.seq(rng.integer(4, top // 4))
+        r1 = rng.integer(2, top // (4 * len(unit)))
+        r2 = r1 + rng.integer(1, top // (8 * len(unit)) + 1)
+        a, b = left + unit * r1 + right, left + unit * r2 + right
+        pairs.append((a, b) if j == 0 else (b, a))
+    p = rng.seq(rng.integer(top // 2, top + 1))
+    t = rng.mutate(p, 0.08)[:top]
+    pairs.append((p[:len(p) // 2] + b"N" + p[len(p) // 2 + 1:], t[:len(t) // 3] + b"N" + t[len(t) // 3 + 1:]))
+    s = rng.seq(rng.integer(1, top // 4 + 1))
+    pairs.append((b"", s) if which % 2 == 0 else (s, b""))
+    assert len(pairs) == SWEEP_PAIRS
+    return pairs
+
+
+def sweep_long(rng):
+    """SWEEP_LONG pairs of 600 to 700 bases (a few more with insertions) at ~4 %: 3 % substitutions and 1 % one-base indels, so that the score stays low enough for
+    the one-wave tier under a deep ring while the rows (window and guard cells) run over several 64-lane chunks."""
+    pairs = []
+    for _ in range(SWEEP_LONG):
+        p = rng.seq(rng.integer(600, 701))
+        r = (rng.u64(len(p)) >> np.uint64(11)).astype(np.float64) / float(1 << 53)
+        extra = (rng.u64(len(p)) >> np.uint64(33)) % np.uint64(3)
+        out = bytearray()
+        for c, ri, x in zip(p, r, extra):
+            if ri < 0.005:
+                continue
+            if ri < 0.01:
+                out.append(b"ACGT"[int(x)])
+                out.append(c)
+            elif ri < 0.04:
+                out.append(b"ACGT"[(b"ACGT".index(c) + 1 + int(x)) % 4])
+            else:
+                out.append(c)
+        pairs.append((p, bytes(out)))
+    return pairs
+
+
+def sweep_over(scores, budget, factor):
+    """Pairs whose score lies above the budget the library runs under: the budget divided by the penalties' common factor, rounded down,
+    and raised to 1 where that is 0 (8 under (9,9) is 1 under (1,1): a score of 9 is within it)."""
+    return int((np.asarray(scores) > max(1, budget // factor) * factor).sum())
+
+
+def sweep_budget_groups(keys, scores, factor, seed, limit=48):
+    """The pairs of a sweep by (parameter key, golden score), for the runs under a budget of exactly that score and of one less:
+    -> [(key, score, indices)], at most `limit` of them in a seeded order in which every key comes at least once.  Left out: score 0,
+    and scores whose budget of one less is not below them once the library has divided it by the penalties' common factor (factor(key))
+    and raised a budget under 1 to 1 -- (score - 1) // factor < 1: there the two budgets are the same run."""
+    by = {}
+    for i, (k, s) in enumerate(zip(keys, scores)):
+        if int(s) > 0 and (int(s) - 1) // factor(k) >= 1:
+            by.setdefault((k, int(s)), []).append(i)
+    order = sorted(by)
+    order = [order[j] for j in np.argsort(Rng(seed).u64(len(order)), kind="stable")]
+    first = {}
+    for ks in order:
+        first.setdefault(ks[0], ks)
+    assert len(first) <= limit
+    chosen = list(first.values()) + [ks for ks in order if first[ks[0]] != ks]
+    return [(k, s, by[(k, s)]) for k, s in chosen[:limit]]
+
+
+#   sweep      SWEEP_PAIRS short pairs (sweep_pairs) per penalty set of SWEEP_PENS, pair i under SWEEP_SPANS[i % 5]; SWEEP_LONG long pairs
+#              (sweep_long) under each of SWEEP_LONG_PENS -- M rings of 33 and 66 rows, either side of the one-wave tier's limit of 64 --, one per span.
+#              Penalties: the cheapest; a coprime set; a common factor of 3; a mismatch deeper than 32; o + e = 64 with a common factor of 2
+#              (the kernels run (1,31,1): an M ring of 33 rows); o + e = 65; e > x; o + e = 63: a ring of 64 rows, the deepest of the one-wave tier.
+SWEEP_SET = "sweep"
+SWEEP_PENS = ((1, 0, 1), (7, 2, 3), (6, 9, 3), (40, 2, 1), (2, 62, 2), (2, 63, 2), (3, 1, 6), (3, 61, 2))
+SWEEP_LONG_PENS = ((2, 62, 2), (2, 63, 2))
+SWEEP_SPANS = ((0, 0, 30, 30), (30, 30, 0, 0), (11, 0, 0, 17), (0, 0, 0, 0), (INT_MAX, INT_MAX, INT_MAX, INT_MAX))
+
+
 def make_set(name):
     """-> (pairs, spans, pens) of a golden set."""
     pairs, spans, pens = [], [], []
-    if name in ("small", ONE_SPAN_SET):
+    if name == SWEEP_SET:
+        rng = Rng(20261001)
+        for j, pen in enumerate(SWEEP_PENS):
+            for i, pair in enumerate(sweep_pairs(rng, sweep_top(ring_depth(pen)), j)):
+                pairs.append(pair)
+                spans.append(SWEEP_SPANS[(i + j) % 5])
+                pens.append(pen)
+        for pen in SWEEP_LONG_PENS:
+            for i, pair in enumerate(sweep_long(rng)):
+                pairs.append(pair)
+                spans.append(SWEEP_SPANS[i % 5])
+                pens.append(pen)
+    elif name in ("small", ONE_SPAN_SET):
         rng = Rng(20260101)
         for i in range(400):
             kind = i % 9

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Regenerates tests/golden/endsfree.{small,wide,ties,small_t50}.alg: WFA2's ends-free score and CIGAR (the reference's WFA2 compiled
+"""Regenerates tests/golden/endsfree.{small,wide,ties,small_t50,sweep}.alg: WFA2's ends-free score and CIGAR (the reference's WFA2 compiled
 in place by oracle/Makefile; run where oracle/_ref exists) for the pairs, spans and penalties that tests/endsfree_ref.py: make_set
 rebuilds -- the sets are described there.  Fixtures are DATA."""
 import os
@@ -16,7 +16,7 @@ def main():
     oracle_lib.build()
     assert oracle_lib.have_ref(), "oracle/_ref not built (reference tree missing?)"
     total = 0
-    for name in ef.SETS + (ef.ONE_SPAN_SET,):
+    for name in ef.SETS + (ef.ONE_SPAN_SET, ef.SWEEP_SET):
         pairs, spans, pens = ef.make_set(name)
         scores, cigars = ef.wfa2_endsfree(pairs, spans, pens)
         ef.write_golden(name, scores, cigars)

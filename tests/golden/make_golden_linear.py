@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Regenerates tests/golden/linear.{small,small_edit,ties,lanes,wide,long}.alg: WFA2's edit, indel and gap-linear score and CIGAR (the
+"""Regenerates tests/golden/linear.{small,small_edit,ties,lanes,wide,long,sweep}.alg: WFA2's edit, indel and gap-linear score and CIGAR (the
 reference's WFA2 compiled in place by oracle/Makefile; run where oracle/_ref exists) for the pairs and metrics that
 tests/linear_ref.py: make_set rebuilds -- the sets are described there.  Fixtures are DATA."""
 import os
@@ -16,7 +16,7 @@ def main():
     oracle_lib.build()
     assert oracle_lib.have_ref(), "oracle/_ref not built (reference tree missing?)"
     total = 0
-    for name in lr.SETS + (lr.LONG_SET,):
+    for name in lr.SETS + (lr.LONG_SET, lr.SWEEP_SET):
         pairs, metrics = lr.make_set(name)
         scores, cigars = lr.wfa2_linear(pairs, metrics)
         if name == "small":

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Regenerates tests/golden/wfadaptive.{small,indel,defaults1k,long,beyond16,small_default}.alg: WFA2's score and CIGAR under its
+"""Regenerates tests/golden/wfadaptive.{small,indel,defaults1k,long,beyond16,small_default,sweep}.alg: WFA2's score and CIGAR under its
 wf-adaptive heuristic (the reference's WFA2 compiled in place by oracle/Makefile; run where oracle/_ref exists) for the pairs,
 heuristics and penalties that tests/wfadaptive_ref.py: make_set rebuilds -- the sets are described there.  Asserts that the heuristic
 changes enough answers in the sets that are meant to show it (wfadaptive_ref.MIN_DIFFERENT).  Fixtures are DATA."""
@@ -17,7 +17,7 @@ def main():
     oracle_lib.build()
     assert oracle_lib.have_ref(), "oracle/_ref not built (reference tree missing?)"
     total = 0
-    for name in wa.ALL_SETS:
+    for name in wa.ALL_SETS + (wa.SWEEP_SET,):
         pairs, heurs, pens = wa.make_set(name)
         scores, cigars = wa.wfa2_wfadaptive(pairs, heurs, pens)
         wa.write_golden(name, scores, cigars)

@@ -13,13 +13,14 @@
 A metric is ("edit",), ("indel",) or ("linear", x, g): match 0, mismatch x > 0, every gap base g > 0; edit is (1, 1); indel is g = 1
 without a mismatch move."""
 import ctypes as C
+import math
 import os
 
 import numpy as np
 
 import oracle_lib
 from affine2p_ref import _elf_symbol_size, _plant
-from endsfree_ref import Rng, parse_cigar
+from endsfree_ref import SWEEP_LONG, SWEEP_PAIRS, Rng, parse_cigar, sweep_long, sweep_pairs, sweep_top
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
@@ -280,12 +281,35 @@ def wfa_linear_model(p, t, metric):
 TIES_METRICS = (EDIT, INDEL, ("linear", 3, 2))
 LANES_METRICS = (EDIT, INDEL, ("linear", 4, 2), ("linear", 5, 1))
 GAP_LENGTHS = (63, 64, 65, 200)
+#   sweep       SWEEP_PAIRS short pairs (endsfree_ref.sweep_pairs) under each of SWEEP_METRICS; SWEEP_LONG long pairs (sweep_long) under
+#               each of SWEEP_LONG_METRICS, M rings of 64 and 65 rows: either side of the one-wave tier's limit.
+SWEEP_SET = "sweep"
+# edit as gap-linear; x > g and x < g, coprime; two sets with a common factor (3 and 9); a mismatch deeper than 32, without and with a
+# deeper gap base; rings of 64, 65 and 66 rows by the mismatch, then by the gap base; a gap base deeper than 32.  WFA2 accepts all fifteen.
+SWEEP_METRICS = tuple(("linear", x, g) for x, g in ((1, 1), (2, 1), (7, 2), (2, 7), (6, 3), (9, 9), (33, 1), (40, 3), (63, 1), (64, 1), (65, 1),
+                                                    (1, 63), (1, 64), (1, 65), (3, 40)))
+SWEEP_LONG_METRICS = (("linear", 63, 1), ("linear", 64, 1))
+
+
+def ring_depth(metric):
+    """Rows of the M ring the kernels run: one per score back to the deepest source, max(x, g) below, and the row being written -- of
+    the penalties without their common factor, which the library divides out first."""
+    x, g = pens_of(metric)
+    return max(x or 0, g) // math.gcd(x or g, g) + 1
 
 
 def make_set(name):
     """-> (pairs, metrics) of a golden set."""
     pairs, metrics = [], []
-    if name in ("small", "small_edit"):
+    if name == SWEEP_SET:
+        rng = Rng(20261003)
+        for j, m in enumerate(SWEEP_METRICS):
+            pairs += sweep_pairs(rng, sweep_top(ring_depth(m)), j)
+            metrics += [m] * SWEEP_PAIRS
+        for m in SWEEP_LONG_METRICS:
+            pairs += sweep_long(rng)
+            metrics += [m] * SWEEP_LONG
+    elif name in ("small", "small_edit"):
         rng = Rng(20260201)
         for i in range(400):
             if i == 9:

@@ -3,6 +3,7 @@ compiled in place) against WFA2 run live; the CIGAR checker; the host-side piece
 the -c verification under two pieces, the command line's usage errors."""
 import ctypes as C
 import hashlib
+import math
 import os
 import subprocess
 
@@ -22,7 +23,7 @@ PAIRS_SHA1 = "cd206f15e1a8941031ee00a0b26883babd908449"      # of the pairs of s
 
 @pytest.fixture(scope="module")
 def sets():
-    return {name: a2.read_golden(name) for name in CIGAR_SETS}
+    return {name: a2.read_golden(name) for name in CIGAR_SETS + (a2.SWEEP_SET,)}
 
 
 def test_golden_sets_have_the_shapes_they_are_for(sets):
@@ -53,14 +54,39 @@ def test_golden_sets_have_the_shapes_they_are_for(sets):
     assert digest == PAIRS_SHA1
 
 
-@pytest.mark.parametrize("name", ALL_SETS)
+def test_the_sweep_has_the_shape_it_is_for(sets):
+    """11 penalty sets of 20 short pairs each and 5 long pairs under M rings of 64 and 66 rows; every set has its byte-compare pair and its
+    empty side; a deep ring gets short pairs (endsfree_ref.sweep_top).  The shapes of the second piece the sets are for are checked on
+    the golden CIGARs: where it always wins every gap run is priced by it, where it never does none is."""
+    g = sets[a2.SWEEP_SET]
+    groups = a2.groups(g)
+    assert len(g["pairs"]) == 11 * 20 + 2 * 5 and set(groups) == set(a2.SWEEP_PENS) and len(a2.SWEEP_PENS) == 11
+    assert sorted(a2.ring_depth(pen) for pen in a2.SWEEP_PENS)[-3:] == [64, 65, 66] and [a2.ring_depth(pen) for pen in a2.SWEEP_LONG_PENS] == [64, 66]
+    assert sum(1 for pen in a2.SWEEP_PENS if math.gcd(*pen) > 1) == 1
+    for pen, idx in groups.items():
+        short = [g["pairs"][i] for i in idx[:20]]
+        assert len(idx) == (25 if pen in a2.SWEEP_LONG_PENS else 20)
+        assert all(600 <= len(p) <= 800 and 600 <= len(t) <= 800 for p, t in (g["pairs"][i] for i in idx[20:]))
+        assert sum(1 for p, t in short if set(p + t) - set(b"ACGT")) == 1 and sum(1 for p, t in short if not p or not t) == 1
+        assert max(max(len(p), len(t)) for p, t in short) <= (48 if a2.ring_depth(pen) >= 60 else 160)
+    runs = lambda pen: [n for i in groups[pen] for n, op in a2.parse_cigar(g["cigars"][i]) if op in "ID"]
+    second = lambda pen, n: pen[3] + n * pen[4] < pen[1] + n * pen[2]
+    assert len(runs((4, 6, 2, 3, 1))) > 20 and all(second((4, 6, 2, 3, 1), n) for n in runs((4, 6, 2, 3, 1)))
+    assert len(runs((2, 1, 1, 1, 3))) > 20 and not any(second((2, 1, 1, 1, 3), n) for n in runs((2, 1, 1, 1, 3)))
+    for pen in ((4, 24, 1, 6, 2), (5, 2, 6, 20, 5), (3, 2, 3, 9, 1)):      # both pieces are used
+        assert any(second(pen, n) for n in runs(pen)) and not all(second(pen, n) for n in runs(pen)), pen
+    assert any(not p for p, _ in g["pairs"]) and any(not t for _, t in g["pairs"])
+    assert os.path.getsize(a2.golden_path(a2.SWEEP_SET)) < (64 << 10)
+
+
+@pytest.mark.parametrize("name", ALL_SETS + (a2.SWEEP_SET,))
 def test_golden_scores_equal_the_dynamic_program(sets, name):
     g = sets[name]
     for i, ((p, t), pen) in enumerate(zip(g["pairs"], g["pens"])):
         assert a2.dp_affine2p_score(p, t, pen) == g["scores"][i], (name, i, pen)
 
 
-@pytest.mark.parametrize("name", CIGAR_SETS)
+@pytest.mark.parametrize("name", CIGAR_SETS + (a2.SWEEP_SET,))
 def test_golden_cigars_are_valid_and_cost_their_score(sets, name):
     g = sets[name]
     for i, ((p, t), pen) in enumerate(zip(g["pairs"], g["pens"])):
@@ -83,7 +109,7 @@ def test_cigar_checker_prices_by_the_cheaper_piece_and_refuses_what_is_wrong():
 
 
 @pytest.mark.skipif(not oracle_lib.have_ref(), reason="the reference's WFA2 is not compiled in place here")
-@pytest.mark.parametrize("name", CIGAR_SETS)
+@pytest.mark.parametrize("name", CIGAR_SETS + (a2.SWEEP_SET,))
 def test_wfa2_run_live_equals_the_golden_files(sets, name):
     g = sets[name]
     scores, cigars = a2.wfa2_affine2p(g["pairs"], g["pens"])

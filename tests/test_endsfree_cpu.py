@@ -3,6 +3,7 @@ compiled in place) against WFA2 run live; the CIGAR checker; the host-side piece
 verification under a span, the command line's usage errors."""
 import ctypes as C
 import hashlib
+import math
 import os
 import subprocess
 
@@ -21,7 +22,7 @@ PAIRS_SHA1 = "9d4f4ef6593fc492d8ae20f3d05d1b5122989528"      # of the pairs of s
 
 @pytest.fixture(scope="module")
 def sets():
-    return {name: ef.read_golden(name) for name in ALL_SETS}
+    return {name: ef.read_golden(name) for name in ALL_SETS + (ef.SWEEP_SET,)}
 
 
 def test_golden_sets_have_the_shapes_they_are_for(sets):
@@ -39,14 +40,35 @@ def test_golden_sets_have_the_shapes_they_are_for(sets):
     assert digest == PAIRS_SHA1
 
 
-@pytest.mark.parametrize("name", ALL_SETS)
+def test_the_sweep_has_the_shape_it_is_for(sets):
+    """8 penalty sets of 20 short pairs each, four under each of the five spans, and 5 long pairs -- one per span -- under M rings of 33 and
+    66 rows; every penalty set has its byte-compare pair and its empty side; a deep ring gets short pairs (endsfree_ref.sweep_top)."""
+    g = sets[ef.SWEEP_SET]
+    groups = ef.groups(g)
+    assert len(g["pairs"]) == 8 * 20 + 2 * 5 and len(ef.SWEEP_PENS) == 8 and len(ef.SWEEP_SPANS) == 5
+    assert set(groups) == {(span, pen) for span in ef.SWEEP_SPANS for pen in ef.SWEEP_PENS}
+    assert (0, 0, 0, 0) in ef.SWEEP_SPANS and (ef.INT_MAX,) * 4 in ef.SWEEP_SPANS
+    assert sorted(ef.ring_depth(pen) for pen in ef.SWEEP_PENS)[-4:] == [33, 41, 64, 66] and sum(1 for pen in ef.SWEEP_PENS if math.gcd(*pen) > 1) == 2
+    assert [ef.ring_depth(pen) for pen in ef.SWEEP_LONG_PENS] == [33, 66]
+    for pen in ef.SWEEP_PENS:
+        idx = [i for i, q in enumerate(g["pens"]) if q == pen]
+        short = [g["pairs"][i] for i in idx[:20]]
+        assert len(idx) == (25 if pen in ef.SWEEP_LONG_PENS else 20)
+        assert all(600 <= len(p) <= 800 and 600 <= len(t) <= 800 for p, t in (g["pairs"][i] for i in idx[20:]))
+        assert sum(1 for p, t in short if set(p + t) - set(b"ACGT")) == 1 and sum(1 for p, t in short if not p or not t) == 1
+        assert max(max(len(p), len(t)) for p, t in short) <= (48 if ef.ring_depth(pen) >= 60 else 160)
+    assert any(not p for p, _ in g["pairs"]) and any(not t for _, t in g["pairs"])
+    assert os.path.getsize(ef.golden_path(ef.SWEEP_SET)) < (64 << 10)
+
+
+@pytest.mark.parametrize("name", ALL_SETS + (ef.SWEEP_SET,))
 def test_golden_scores_equal_the_dynamic_program(sets, name):
     g = sets[name]
     for i, ((p, t), span, pen) in enumerate(zip(g["pairs"], g["spans"], g["pens"])):
         assert ef.dp_endsfree_score(p, t, pen, span) == g["scores"][i], (name, i, span, pen)
 
 
-@pytest.mark.parametrize("name", ALL_SETS)
+@pytest.mark.parametrize("name", ALL_SETS + (ef.SWEEP_SET,))
 def test_golden_cigars_are_valid_and_cost_their_score(sets, name):
     g = sets[name]
     for i, ((p, t), span, pen) in enumerate(zip(g["pairs"], g["spans"], g["pens"])):
@@ -66,7 +88,7 @@ def test_cigar_checker_refuses_what_is_wrong():
 
 
 @pytest.mark.skipif(not oracle_lib.have_ref(), reason="the reference's WFA2 is not compiled in place here")
-@pytest.mark.parametrize("name", ALL_SETS)
+@pytest.mark.parametrize("name", ALL_SETS + (ef.SWEEP_SET,))
 def test_wfa2_run_live_equals_the_golden_files(sets, name):
     g = sets[name]
     for mode in (0, 1):

@@ -2,6 +2,7 @@
 seam and the CLI, against WFA2's gap_affine_2p scores and CIGARs (tests/golden/affine2p.*, made by
 tests/golden/make_golden_affine2p.py; the sets are described in tests/affine2p_ref.py)."""
 import ctypes as C
+import math
 import os
 import subprocess
 import sys
@@ -12,6 +13,7 @@ import pytest
 import affine2p_ref as a2
 import oracle_lib
 import wfagpu
+from endsfree_ref import sweep_budget_groups, sweep_over
 
 pytestmark = pytest.mark.gpu
 PKG = os.path.dirname(wfagpu.LIB_PATH)
@@ -297,3 +299,89 @@ def test_gap_affine_calls_never_load_the_two_piece_code_objects():
     assert r.returncode == 0, r.stderr[-2000:]
     seen = dict(line.rsplit(" ", 1) for line in r.stdout.splitlines() if line[:3] in ("gap", "two"))
     assert seen == {"gap-affine": "0", "two-piece scores": "2", "two-piece cigars": "6"}, r.stdout
+
+
+# ---- the sweep: eleven penalty sets and tight budgets (affine2p_ref.SWEEP_PENS) ---------------------------------------------------
+SWEEP_PATHS = ["as shipped", "min_tier1", "min_tier2", "min_tier3", "max_error8"]
+
+
+@pytest.fixture(scope="module")
+def sweep():
+    return a2.read_golden(a2.SWEEP_SET)
+
+
+def _factor(pen):
+    return math.gcd(*pen)
+
+
+@pytest.mark.parametrize("cigar", [False, True])
+@pytest.mark.parametrize("path", SWEEP_PATHS)
+def test_sweep_golden(sweep, cigar, path):
+    """Every penalty set of the sweep as one call under a budget of its largest golden score plus 1 (max_error8: of 8) -- as shipped and
+    forced through the wider tiers: WFA2's scores and CIGAR bytes."""
+    g = sweep
+    al = wfagpu.DeviceAligner(0, **({"min_tier": int(path[-1])} if path.startswith("min_tier") else {}))
+    try:
+        for pen, idx in a2.groups(g).items():
+            budget = 8 if path == "max_error8" else int(g["scores"][idx].max()) + 1
+            scores, cigars, (st,) = _run_set(al, g, cigar, budget, only=set(idx))
+            _check_set(g, scores, cigars, cigar, only=set(idx))
+            if path.startswith("min_tier"):
+                assert sum(st.pairs_tier[:int(path[-1])]) == 0, pen
+            if path == "max_error8":
+                assert st.pairs_retried >= sweep_over(g["scores"][idx], 8, _factor(pen)), pen
+    finally:
+        al.close()
+
+
+def test_ring_depth_on_either_side_of_the_one_wave_limit(sweep):
+    """plan_tier keeps an M ring of more than 64 rows (max(x, o1 + e1, o2 + e2) + 1: affine2p_ref.ring_depth) off the one-wave tier: as
+    shipped, under a budget just above its golden scores, a penalty set whose ring has at most 64 rows -- (2,3,1,62,1) -- has pairs
+    on tier 0 and one with a deeper ring -- (2,3,1,63,1), (2,3,1,64,1) -- has none, and both give WFA2's bytes."""
+    g = sweep
+    al = wfagpu.DeviceAligner(0)
+    try:
+        depths = set()
+        for pen, idx in a2.groups(g).items():
+            scores, cigars, (st,) = _run_set(al, g, True, int(g["scores"][idx].max()) + 1, only=set(idx))
+            _check_set(g, scores, cigars, True, only=set(idx))
+            depth = a2.ring_depth(pen)
+            depths.add(depth)
+            assert (st.pairs_tier[0] > 0) == (depth <= 64), (pen, depth, list(st.pairs_tier))
+        assert {64, 65, 66} <= depths
+    finally:
+        al.close()
+
+
+def test_score_budget_window_is_exact(sweep):
+    """The counterpart of test_gpu_parity.py's test_score_budget_window_is_exact: the pairs of a penalty set that share a golden score run
+    under a budget of exactly that score -- the ring of window_width_2p has to hold them: no pair comes back for a wider one -- and
+    of one less -- every pair does --, and give WFA2's bytes both times.  (6,9,3,30,3) runs as (2,3,1,10,1) with the budget divided by
+    3, rounded down: score and score - 1 still fall on either side."""
+    g = sweep
+    chosen = sweep_budget_groups(g["pens"], g["scores"], _factor, seed=20261012)
+    assert {k for k, _, _ in chosen} == set(a2.SWEEP_PENS) and len(chosen) <= 48
+    al = wfagpu.DeviceAligner(0)
+    try:
+        for pen, score, idx in chosen:
+            for budget in (score, score - 1):
+                scores, cigars, (st,) = _run_set(al, g, True, budget, only=set(idx))
+                _check_set(g, scores, cigars, True, only=set(idx))
+                assert st.pairs_retried == (0 if budget == score else len(idx)), (pen, score, budget, len(idx))
+    finally:
+        al.close()
+
+
+def test_sweep_behind_the_launch_seam(sweep):
+    """wfagpu_amd_configure_affine2p with penalties that have a common factor and with a ring deeper than 64 rows, through
+    launch_alignments with a batch size that cuts the call: the golden bytes."""
+    g = sweep
+    groups = a2.groups(g)
+    try:
+        for pen in ((6, 9, 3, 30, 3), (2, 3, 1, 64, 1)):
+            idx = groups[pen]
+            wfagpu.configure_affine2p(pen)
+            s, c = _launch([g["pairs"][i] for i in idx], (2, 3, 1), True, int(g["scores"][idx].max()) + 1, 7)
+            assert np.array_equal(s, g["scores"][idx]) and c == [g["cigars"][i] for i in idx], pen
+    finally:
+        wfagpu.configure_affine2p()

@@ -2,6 +2,7 @@
 launch_alignments* seam and the CLI, against WFA2's ends-free scores and CIGARs (tests/golden/endsfree.*, made by
 tests/golden/make_golden_endsfree.py; the sets are described in tests/endsfree_ref.py)."""
 import ctypes as C
+import math
 import os
 import random
 import subprocess
@@ -232,3 +233,99 @@ def test_cli_ends_free(sets, tmp_path):
     assert "Incorrect=0" in r.stderr and all(tok == "Incorrect=0" for tok in r.stderr.split() if tok.startswith("Incorrect="))
     got = open(out).read().splitlines()
     assert got == [f"{-int(g['scores'][i])}\t{g['cigars'][i]}" for i in keep]
+
+
+# ---- the sweep: eight penalty sets under five spans and tight budgets (endsfree_ref.SWEEP_PENS, SWEEP_SPANS) -----------------------
+SWEEP_PATHS = ["as shipped", "min_tier1", "min_tier2", "min_tier3", "max_error8"]
+
+
+@pytest.fixture(scope="module")
+def sweep():
+    return ef.read_golden(ef.SWEEP_SET)
+
+
+def _factor(key):
+    return math.gcd(*key[1])
+
+
+@pytest.mark.parametrize("cigar", [False, True])
+@pytest.mark.parametrize("path", SWEEP_PATHS)
+def test_sweep_golden(sweep, cigar, path):
+    """Every (span, penalties) group of the sweep as one call under a budget of its largest golden score plus 1 (max_error8: of 8) -- as
+    shipped and forced through the wider tiers: WFA2's scores and CIGAR bytes."""
+    g = sweep
+    al = wfagpu.DeviceAligner(0, **({"min_tier": int(path[-1])} if path.startswith("min_tier") else {}))
+    try:
+        for key, idx in ef.groups(g).items():
+            budget = 8 if path == "max_error8" else int(g["scores"][idx].max()) + 1
+            scores, cigars, ends, (st,) = _run_set(al, g, cigar, budget, only=set(idx))
+            _check_set(g, scores, cigars, ends, cigar, only=set(idx))
+            if path.startswith("min_tier"):
+                assert sum(st.pairs_tier[:int(path[-1])]) == 0, key
+            if path == "max_error8":
+                assert st.pairs_retried >= ef.sweep_over(g["scores"][idx], 8, _factor(key)), key
+    finally:
+        al.close()
+
+
+def test_ring_depth_on_either_side_of_the_one_wave_limit(sweep):
+    """plan_tier keeps an M ring of more than 64 rows (max(x, o + e) + 1: endsfree_ref.ring_depth) off the one-wave tier: as shipped,
+    under budgets just above the golden scores, a penalty set whose ring has at most 64 rows has pairs on tier 0 and no call of one
+    with a deeper ring has any -- and both give WFA2's bytes.  The rows are those of the penalties without their common factor:
+    (2,62,2) runs as (1,31,1), 33 rows, (3,61,2) is the set with 64 and (2,63,2) has 66.  Counted per penalty set, over its five spans:
+    the window of a span is wider by the free bases, and the all-free span of a 700-base pair is every diagonal there is, which no
+    one-wave ring holds."""
+    g = sweep
+    al = wfagpu.DeviceAligner(0)
+    try:
+        tier0, depths = {}, {}
+        for (span, pen), idx in ef.groups(g).items():
+            scores, cigars, ends, (st,) = _run_set(al, g, True, int(g["scores"][idx].max()) + 1, only=set(idx))
+            _check_set(g, scores, cigars, ends, True, only=set(idx))
+            depths[pen] = ef.ring_depth(pen)
+            tier0[pen] = tier0.get(pen, 0) + st.pairs_tier[0]
+            assert depths[pen] <= 64 or st.pairs_tier[0] == 0, (span, pen, list(st.pairs_tier))
+        assert set(tier0) == set(ef.SWEEP_PENS) and {64, 66} <= set(depths.values())
+        for pen in ef.SWEEP_PENS:
+            assert (tier0[pen] > 0) == (depths[pen] <= 64), (pen, depths[pen], tier0[pen])
+    finally:
+        al.close()
+
+
+def test_score_budget_window_is_exact(sweep):
+    """The counterpart of test_gpu_parity.py's test_score_budget_window_is_exact: the pairs of a (span, penalties) group that share a
+    golden score run under a budget of exactly that score and of one less -- every pair comes back for a wider ring then --, and give
+    WFA2's bytes both times.  At the score itself only the results are asserted: the ends-free window is a bound for the longest pair
+    of the call (plan_tier), and a shorter pair whose own window is wider legitimately comes back as a window failure.  (6,9,3) runs as
+    (2,3,1) and (2,62,2) as (1,31,1) with the budget divided by the factor, rounded down: score and score - 1 still fall on either
+    side.  (The all-free span scores 0 everywhere and has no budget to run under.)"""
+    g = sweep
+    chosen = ef.sweep_budget_groups(list(zip(g["spans"], g["pens"])), g["scores"], _factor, seed=20261011)
+    assert {k[1] for k, _, _ in chosen} == set(ef.SWEEP_PENS) and {k[0] for k, _, _ in chosen} == set(ef.SWEEP_SPANS[:4]) and len(chosen) <= 48
+    al = wfagpu.DeviceAligner(0)
+    try:
+        for key, score, idx in chosen:
+            for budget in (score, score - 1):
+                scores, cigars, ends, (st,) = _run_set(al, g, True, budget, only=set(idx))
+                _check_set(g, scores, cigars, ends, True, only=set(idx))
+                if budget < score:
+                    assert st.pairs_retried == len(idx), (key, score, budget, len(idx))
+    finally:
+        al.close()
+
+
+def test_sweep_behind_the_launch_seam(sweep):
+    """wfagpu_amd_configure_span with each span of the sweep under penalties that have a common factor and under a ring deeper than 64
+    rows, through launch_alignments with a batch size that cuts the call: the golden bytes."""
+    g = sweep
+    groups = ef.groups(g)
+    try:
+        for pen in ((6, 9, 3), (2, 63, 2)):
+            for span in ef.SWEEP_SPANS:
+                idx = groups[(span, pen)]
+                pb, pe, tb, te = span
+                wfagpu.configure_span(pattern_begin_free=pb, pattern_end_free=pe, text_begin_free=tb, text_end_free=te)
+                s, c = _launch([g["pairs"][i] for i in idx], pen, True, int(g["scores"][idx].max()) + 1, 3)
+                assert np.array_equal(s, g["scores"][idx]) and c == [g["cigars"][i] for i in idx], (span, pen)
+    finally:
+        wfagpu.configure_span()

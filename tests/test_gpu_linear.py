@@ -2,6 +2,7 @@
 launch_alignments* seam and the CLI, against WFA2's scores and CIGARs (tests/golden/linear.*, made by
 tests/golden/make_golden_linear.py; the sets are described in tests/linear_ref.py)."""
 import ctypes as C
+import math
 import os
 import subprocess
 import sys
@@ -12,6 +13,7 @@ import pytest
 import linear_ref as lr
 import oracle_lib
 import wfagpu
+from endsfree_ref import sweep_budget_groups, sweep_over
 
 pytestmark = pytest.mark.gpu
 PKG = os.path.dirname(wfagpu.LIB_PATH)
@@ -294,3 +296,89 @@ def test_other_calls_never_load_the_one_component_code_objects():
     assert r.returncode == 0, r.stderr[-2000:]
     seen = dict(line.rsplit(" ", 1) for line in r.stdout.splitlines() if line[:4] in ("othe", "edit"))
     assert seen == {"others": "0", "edit scores": "16", "edit cigars": "48"}, r.stdout
+
+
+# ---- the sweep: thirteen (x, g) and tight budgets (linear_ref.SWEEP_METRICS) ------------------------------------------------------
+SWEEP_PATHS = ["as shipped", "min_tier1", "min_tier2", "min_tier3", "max_error8"]
+
+
+@pytest.fixture(scope="module")
+def sweep():
+    return lr.read_golden(lr.SWEEP_SET)
+
+
+def _factor(metric):
+    return math.gcd(*lr.pens_of(metric))
+
+
+@pytest.mark.parametrize("cigar", [False, True])
+@pytest.mark.parametrize("path", SWEEP_PATHS)
+def test_sweep_golden(sweep, cigar, path):
+    """Every metric of the sweep as one call under a budget of its largest golden score plus 1 (max_error8: of 8) -- as shipped and
+    forced through the wider tiers: WFA2's scores and CIGAR bytes."""
+    g = sweep
+    al = wfagpu.DeviceAligner(0, **({"min_tier": int(path[-1])} if path.startswith("min_tier") else {}))
+    try:
+        for metric, idx in lr.groups(g).items():
+            budget = 8 if path == "max_error8" else int(g["scores"][idx].max()) + 1
+            scores, cigars, (st,) = _run_set(al, g, cigar, budget, only=set(idx))
+            _check_set(g, scores, cigars, cigar, only=set(idx))
+            if path.startswith("min_tier"):
+                assert sum(st.pairs_tier[:int(path[-1])]) == 0, metric
+            if path == "max_error8":
+                assert st.pairs_retried >= sweep_over(g["scores"][idx], 8, _factor(metric)), metric
+    finally:
+        al.close()
+
+
+def test_ring_depth_on_either_side_of_the_one_wave_limit(sweep):
+    """plan_tier keeps an M ring of more than 64 rows (max(x, g) + 1: linear_ref.ring_depth) off the one-wave tier: as shipped, under a
+    budget just above its golden scores, a metric whose ring has at most 64 rows -- (63,1), (1,63) -- has pairs on tier 0 and one with
+    a deeper ring -- (64,1), (1,64) -- has none, and both give WFA2's bytes."""
+    g = sweep
+    al = wfagpu.DeviceAligner(0)
+    try:
+        depths = set()
+        for metric, idx in lr.groups(g).items():
+            scores, cigars, (st,) = _run_set(al, g, True, int(g["scores"][idx].max()) + 1, only=set(idx))
+            _check_set(g, scores, cigars, True, only=set(idx))
+            depth = lr.ring_depth(metric)
+            depths.add(depth)
+            assert (st.pairs_tier[0] > 0) == (depth <= 64), (metric, depth, list(st.pairs_tier))
+        assert {64, 65} <= depths
+    finally:
+        al.close()
+
+
+def test_score_budget_window_is_exact(sweep):
+    """The counterpart of test_gpu_parity.py's test_score_budget_window_is_exact: the pairs of a metric that share a golden score run under
+    a budget of exactly that score -- the narrowest ring that has to hold them: no pair comes back for a wider one -- and of one
+    less -- every pair does --, and give WFA2's bytes both times.  (6,3) and (9,9) run as (2,1) and (1,1) with the budget divided by 3
+    and 9, rounded down: score and score - 1 still fall on either side."""
+    g = sweep
+    chosen = sweep_budget_groups(g["metrics"], g["scores"], _factor, seed=20261013)
+    assert {k for k, _, _ in chosen} == set(lr.SWEEP_METRICS) and len(chosen) <= 48
+    al = wfagpu.DeviceAligner(0)
+    try:
+        for metric, score, idx in chosen:
+            for budget in (score, score - 1):
+                scores, cigars, (st,) = _run_set(al, g, True, budget, only=set(idx))
+                _check_set(g, scores, cigars, True, only=set(idx))
+                assert st.pairs_retried == (0 if budget == score else len(idx)), (metric, score, budget, len(idx))
+    finally:
+        al.close()
+
+
+def test_sweep_behind_the_launch_seam(sweep):
+    """wfagpu_amd_configure_linear with a metric that has a common factor and with one whose ring is deeper than 64 rows, through
+    launch_alignments with a batch size that cuts the call: the golden bytes."""
+    g = sweep
+    groups = lr.groups(g)
+    try:
+        for metric in (("linear", 6, 3), ("linear", 64, 1)):
+            idx = groups[metric]
+            wfagpu.configure_linear(metric)
+            s, c = _launch([g["pairs"][i] for i in idx], (2, 3, 1), True, int(g["scores"][idx].max()) + 1, 7)
+            assert np.array_equal(s, g["scores"][idx]) and c == [g["cigars"][i] for i in idx], metric
+    finally:
+        wfagpu.configure_linear()

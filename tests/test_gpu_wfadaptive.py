@@ -3,6 +3,7 @@ seam and the CLI, against WFA2's scores and CIGARs under the same heuristic (tes
 tests/golden/make_golden_wfadaptive.py; the sets are described in tests/wfadaptive_ref.py).  The heuristic is deterministic: every
 comparison is byte for byte."""
 import ctypes as C
+import math
 import os
 import subprocess
 import sys
@@ -13,6 +14,7 @@ import pytest
 import oracle_lib
 import wfadaptive_ref as wa
 import wfagpu
+from endsfree_ref import sweep_budget_groups, sweep_over
 
 pytestmark = pytest.mark.gpu
 PKG = os.path.dirname(wfagpu.LIB_PATH)
@@ -378,3 +380,94 @@ def test_only_adaptive_calls_load_the_adaptive_code_object():
     assert seen == {"gap-affine": "0", "others": "7"}, out
     seen, out = _fresh(_FRESH_ADAPTIVE)
     assert seen == {"adaptive scores": "8", "adaptive cigars": "8", "primed": "8"}, out
+
+
+# ---- the sweep: seven penalty sets under five heuristics and tight budgets (wfadaptive_ref.SWEEP_PENS, SWEEP_HEUR) -----------------
+SWEEP_PATHS = ["as shipped", "min_tier1", "min_tier2", "min_tier3", "max_error8"]
+
+
+@pytest.fixture(scope="module")
+def sweep():
+    return wa.read_golden(wa.SWEEP_SET)
+
+
+def _factor(key):
+    return math.gcd(*key[1])
+
+
+@pytest.mark.parametrize("cigar", [False, True])
+@pytest.mark.parametrize("path", SWEEP_PATHS)
+def test_sweep_golden(sweep, cigar, path):
+    """Every (heuristic, penalties) group of the sweep as one call under a budget of its largest golden score plus 1 (max_error8: of 8) --
+    as shipped and forced through the wider tiers: WFA2's scores and CIGAR bytes under the same heuristic."""
+    g = sweep
+    al = wfagpu.DeviceAligner(0, **({"min_tier": int(path[-1])} if path.startswith("min_tier") else {}))
+    try:
+        for key, idx in wa.groups(g).items():
+            budget = 8 if path == "max_error8" else int(g["scores"][idx].max()) + 1
+            scores, cigars, (st,) = _run_set(al, g, cigar, budget, only=set(idx))
+            _check_set(g, scores, cigars, cigar, only=set(idx))
+            if path.startswith("min_tier"):
+                assert sum(st.pairs_tier[:int(path[-1])]) == 0, key
+            if path == "max_error8":
+                assert st.pairs_retried >= sweep_over(g["scores"][idx], 8, _factor(key)), key
+    finally:
+        al.close()
+
+
+def test_ring_depth_on_either_side_of_the_one_wave_limit(sweep):
+    """plan_tier keeps an M ring of more than 64 rows (max(x, o + e) + 1: endsfree_ref.ring_depth) off the one-wave tier: as shipped,
+    under budgets just above the golden scores, a penalty set whose ring has at most 64 rows -- (2,62,1) has 64 -- has pairs on
+    tier 0 and no call of one with a deeper ring -- (2,64,1) has 66 -- has any, and both give WFA2's bytes.  Counted per penalty set, over its five heuristics (the ring of window_width_ad is twice the exact one: a
+    call with a 700-base pair may outgrow the one-wave tier whatever the depth)."""
+    g = sweep
+    al = wfagpu.DeviceAligner(0)
+    try:
+        tier0, depths = {}, {}
+        for (heur, pen), idx in wa.groups(g).items():
+            scores, cigars, (st,) = _run_set(al, g, True, int(g["scores"][idx].max()) + 1, only=set(idx))
+            _check_set(g, scores, cigars, True, only=set(idx))
+            depths[pen] = wa.ring_depth(pen)
+            tier0[pen] = tier0.get(pen, 0) + st.pairs_tier[0]
+            assert depths[pen] <= 64 or st.pairs_tier[0] == 0, (heur, pen, list(st.pairs_tier))
+        assert set(tier0) == set(wa.SWEEP_PENS) and {64, 66} <= set(depths.values())
+        for pen in wa.SWEEP_PENS:
+            assert (tier0[pen] > 0) == (depths[pen] <= 64), (pen, depths[pen], tier0[pen])
+    finally:
+        al.close()
+
+
+def test_score_budget_window_is_exact(sweep):
+    """The counterpart of test_gpu_parity.py's test_score_budget_window_is_exact: the pairs of a (heuristic, penalties) group that share
+    a golden score -- the heuristic's own, not the optimum -- run under a budget of exactly that score -- the ring of window_width_ad
+    has to hold them: no pair comes back for a wider one -- and of one less -- every pair does --, and give WFA2's bytes both times.
+    (6,9,3) runs as (2,3,1) with the budget divided by 3, rounded down, and the steps between cut-offs counted in the reduced scores:
+    score and score - 1 still fall on either side."""
+    g = sweep
+    chosen = sweep_budget_groups(list(zip(g["heurs"], g["pens"])), g["scores"], _factor, seed=20261014)
+    assert {k for k, _, _ in chosen} == {(h, pen) for h in wa.SWEEP_HEUR for pen in wa.SWEEP_PENS} and len(chosen) <= 48
+    al = wfagpu.DeviceAligner(0)
+    try:
+        for key, score, idx in chosen:
+            for budget in (score, score - 1):
+                scores, cigars, (st,) = _run_set(al, g, True, budget, only=set(idx))
+                _check_set(g, scores, cigars, True, only=set(idx))
+                assert st.pairs_retried == (0 if budget == score else len(idx)), (key, score, budget, len(idx))
+    finally:
+        al.close()
+
+
+def test_sweep_behind_the_launch_seam(sweep):
+    """wfagpu_amd_configure_wfadaptive with each heuristic of the sweep under penalties that have a common factor and under a ring
+    deeper than 64 rows, through launch_alignments with a batch size that cuts the call: the golden bytes."""
+    g = sweep
+    groups = wa.groups(g)
+    try:
+        for pen in ((6, 9, 3), (2, 64, 1)):
+            for heur in wa.SWEEP_HEUR:
+                idx = groups[(heur, pen)]
+                wfagpu.configure_wfadaptive(heur)
+                s, c = _launch([g["pairs"][i] for i in idx], pen, True, int(g["scores"][idx].max()) + 1, 3)
+                assert np.array_equal(s, g["scores"][idx]) and c == [g["cigars"][i] for i in idx], (heur, pen)
+    finally:
+        wfagpu.configure_wfadaptive()

@@ -2,6 +2,7 @@
 M-only wavefront search and (where the reference is compiled in place) WFA2 run live; the host-side pieces -- the new symbols,
 wfagpu_amd_configure_linear, the -c checkers, the command line's usage errors."""
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -19,7 +20,7 @@ ALL_SETS = lr.SETS + (lr.LONG_SET,)
 
 @pytest.fixture(scope="module")
 def sets():
-    return {name: lr.read_golden(name) for name in ALL_SETS}
+    return {name: lr.read_golden(name) for name in ALL_SETS + (lr.SWEEP_SET,)}
 
 
 def test_golden_sets_have_the_shapes_they_are_for(sets):
@@ -55,14 +56,37 @@ def test_no_x_in_a_golden_indel_cigar_and_indel_is_not_gap_linear_2_1(sets):
     assert 4 * differ >= len(idx)
 
 
-@pytest.mark.parametrize("name", ["small", "ties", "lanes"])
+def test_the_sweep_has_the_shape_it_is_for(sets):
+    """15 metrics of 20 short pairs each and 5 long pairs on either side of the one-wave tier's ring depth; every metric has its
+    byte-compare pair and its empty side; the planted gaps start at one base, alternate sides and reach 60 bases where the pairs are
+    long enough; a deep ring gets short pairs (endsfree_ref.sweep_top)."""
+    g = sets[lr.SWEEP_SET]
+    groups = lr.groups(g)
+    assert len(g["pairs"]) == 15 * 20 + 2 * 5 and set(groups) == set(lr.SWEEP_METRICS) and len(lr.SWEEP_METRICS) == 15
+    assert sorted(lr.ring_depth(m) for m in lr.SWEEP_LONG_METRICS) == [64, 65]
+    assert sorted(lr.ring_depth(m) for m in lr.SWEEP_METRICS)[-7:] == [41, 64, 64, 65, 65, 66, 66]
+    assert {math.gcd(m[1], m[2]) for m in lr.SWEEP_METRICS} == {1, 3, 9}
+    for m, idx in groups.items():
+        short = [g["pairs"][i] for i in idx if max(map(len, g["pairs"][i])) <= 160]
+        assert len(short) == 20 and len(idx) == (25 if m in lr.SWEEP_LONG_METRICS else 20)
+        assert all(600 <= len(p) <= 800 and 600 <= len(t) <= 800 for p, t in (g["pairs"][i] for i in idx[20:]))
+        assert sum(1 for p, t in short if set(p + t) - set(b"ACGT")) == 1 and sum(1 for p, t in short if not p or not t) == 1
+        assert max(max(len(p), len(t)) for p, t in short) <= (48 if lr.ring_depth(m) >= 60 else 160)
+        gaps = [abs(len(p) - len(t)) for p, t in short[12:16]]
+        assert gaps[0] == 1 and gaps[1] == max(gaps) and (gaps[1] == 60 or lr.ring_depth(m) >= 60)
+        assert [len(p) < len(t) for p, t in short[12:16]] == [True, False, True, False]
+    assert any(not p for p, _ in g["pairs"]) and any(not t for _, t in g["pairs"])
+    assert os.path.getsize(lr.golden_path(lr.SWEEP_SET)) < (64 << 10)
+
+
+@pytest.mark.parametrize("name", ["small", "ties", "lanes", lr.SWEEP_SET])
 def test_golden_scores_equal_the_dynamic_program(sets, name):
     g = sets[name]
     for i, ((p, t), m) in enumerate(zip(g["pairs"], g["metrics"])):
         assert lr.dp_linear_score(p, t, *lr.pens_of(m)) == g["scores"][i], (name, i, m)
 
 
-@pytest.mark.parametrize("name", ALL_SETS)
+@pytest.mark.parametrize("name", ALL_SETS + (lr.SWEEP_SET,))
 def test_golden_cigars_are_valid_and_cost_their_score(sets, name):
     g = sets[name]
     for i, ((p, t), m) in enumerate(zip(g["pairs"], g["metrics"])):
@@ -70,7 +94,7 @@ def test_golden_cigars_are_valid_and_cost_their_score(sets, name):
         assert ok and cost == g["scores"][i], (name, i, m)
 
 
-@pytest.mark.parametrize("name", lr.SETS)
+@pytest.mark.parametrize("name", lr.SETS + (lr.SWEEP_SET,))
 def test_the_model_without_pruning_gives_wfa2s_bytes(sets, name):
     """No exact pruning of wide edit rows, mismatch > deletion > insertion on equal offsets: what the kernels restate."""
     g = sets[name]
@@ -80,7 +104,7 @@ def test_the_model_without_pruning_gives_wfa2s_bytes(sets, name):
 
 
 @pytest.mark.skipif(not oracle_lib.have_ref(), reason="the reference's WFA2 is not compiled in place here")
-@pytest.mark.parametrize("name", ALL_SETS)
+@pytest.mark.parametrize("name", ALL_SETS + (lr.SWEEP_SET,))
 def test_wfa2_run_live_equals_the_golden_files(sets, name):
     g = sets[name]
     scores, cigars = lr.wfa2_linear(g["pairs"], g["metrics"])

@@ -2,6 +2,7 @@
 against WFA2 run live; the host-side pieces -- the new symbols, wfagpu_amd_configure_wfadaptive, the relaxed -c verdict, the command
 line's usage errors."""
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -18,7 +19,7 @@ CLI = os.path.join(PKG, "bin", "wfa.affine.gpu")
 
 @pytest.fixture(scope="module")
 def sets():
-    return {name: wa.read_golden(name) for name in wa.ALL_SETS}
+    return {name: wa.read_golden(name) for name in wa.ALL_SETS + (wa.SWEEP_SET,)}
 
 
 def test_golden_sets_have_the_shapes_they_are_for(sets):
@@ -40,6 +41,27 @@ def test_golden_sets_have_the_shapes_they_are_for(sets):
     assert sum(os.path.getsize(wa.golden_path(name)) for name in wa.ALL_SETS) < (1 << 20)
 
 
+def test_the_sweep_has_the_shape_it_is_for(sets):
+    """7 penalty sets of 20 short pairs each, four under each of the five heuristics, and 5 long pairs -- one per heuristic -- under M rings
+    of 8 and 66 rows; every penalty set has its byte-compare pair and its empty side; a deep ring gets short pairs."""
+    g = sets[wa.SWEEP_SET]
+    groups = wa.groups(g)
+    assert len(g["pairs"]) == 7 * 20 + 2 * 5 and len(wa.SWEEP_PENS) == 7 and len(wa.SWEEP_HEUR) == 5
+    assert set(groups) == {(h, pen) for h in wa.SWEEP_HEUR for pen in wa.SWEEP_PENS}
+    depth = wa.ring_depth
+    assert sorted(depth(pen) for pen in wa.SWEEP_PENS)[-3:] == [41, 64, 66] and sum(1 for pen in wa.SWEEP_PENS if math.gcd(*pen) > 1) == 1
+    assert sorted(depth(pen) for pen in wa.SWEEP_LONG_PENS) == [8, 66]
+    for pen in wa.SWEEP_PENS:
+        idx = [i for i, q in enumerate(g["pens"]) if q == pen]
+        short = [g["pairs"][i] for i in idx[:20]]
+        assert len(idx) == (25 if pen in wa.SWEEP_LONG_PENS else 20)
+        assert all(600 <= len(p) <= 800 and 600 <= len(t) <= 800 for p, t in (g["pairs"][i] for i in idx[20:]))
+        assert sum(1 for p, t in short if set(p + t) - set(b"ACGT")) == 1 and sum(1 for p, t in short if not p or not t) == 1
+        assert max(max(len(p), len(t)) for p, t in short) <= (48 if depth(pen) >= 60 else 160)
+    assert any(not p for p, _ in g["pairs"]) and any(not t for _, t in g["pairs"])
+    assert os.path.getsize(wa.golden_path(wa.SWEEP_SET)) < (64 << 10)
+
+
 @pytest.mark.parametrize("name", sorted(wa.MIN_DIFFERENT))
 def test_the_heuristic_changes_answers_in_the_sets_that_are_meant_to_show_it(sets, name):
     """A heuristic test proves nothing where the heuristic changes nothing: pairs whose stored score lies above the exact optimum
@@ -47,7 +69,7 @@ def test_the_heuristic_changes_answers_in_the_sets_that_are_meant_to_show_it(set
     assert wa.count_different(sets[name], cigars_too=name == "defaults1k") >= wa.MIN_DIFFERENT[name]
 
 
-@pytest.mark.parametrize("name", wa.ALL_SETS)
+@pytest.mark.parametrize("name", wa.ALL_SETS + (wa.SWEEP_SET,))
 def test_golden_cigars_are_valid_cost_their_score_and_no_score_is_below_the_optimum(sets, name):
     g = sets[name]
     opt, _ = wa.exact_answers(g["pairs"], g["pens"])
@@ -58,7 +80,7 @@ def test_golden_cigars_are_valid_cost_their_score_and_no_score_is_below_the_opti
 
 
 @pytest.mark.skipif(not oracle_lib.have_ref(), reason="the reference's WFA2 is not compiled in place here")
-@pytest.mark.parametrize("name", wa.ALL_SETS)
+@pytest.mark.parametrize("name", wa.ALL_SETS + (wa.SWEEP_SET,))
 def test_wfa2_run_live_equals_the_golden_files(sets, name):
     g = sets[name]
     scores, cigars = wa.wfa2_wfadaptive(g["pairs"], g["heurs"], g["pens"])

@@ -14,7 +14,7 @@ import os
 import numpy as np
 
 import oracle_lib
-from endsfree_ref import Rng
+from endsfree_ref import Rng, ring_depth, sweep_long, sweep_pairs, sweep_top
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
@@ -27,7 +27,15 @@ SETS = ("small", "indel", "defaults1k", "long", "beyond16")
 ONE_SET, ONE_HEUR, ONE_PEN = "small_default", (10, 10, 1), (2, 3, 1)
 ALL_SETS = SETS + (ONE_SET,)
 # pairs of a set whose heuristic answer must differ from the exact one (score above the optimum; defaults1k: score or CIGAR)
-MIN_DIFFERENT = {"small": 20, "indel": 5, "long": 2, "defaults1k": 2}
+MIN_DIFFERENT = {"small": 20, "indel": 5, "long": 2, "defaults1k": 2, "sweep": 10}
+# the sweep: the cheapest penalties; e > x; a coprime set; a common factor of 3 (the heuristic counts its steps in scores: the reduced
+# search has to cut where WFA2 does); a mismatch deeper than 32; o + e = 65, an M ring of 66 rows: beyond the one-wave tier's 64; o + e = 63, the
+# deepest ring of that tier
+SWEEP_SET = "sweep"
+SWEEP_PENS = ((1, 0, 1), (3, 1, 4), (7, 2, 3), (6, 9, 3), (40, 2, 1), (2, 64, 1), (2, 62, 1))
+SWEEP_LONG_PENS = ((7, 2, 3), (2, 64, 1))
+# WFA2's defaults; the tightest heuristic there is; three steps between cut-offs; seven; a length few rows of short pairs reach
+SWEEP_HEUR = ((10, 50, 1), (1, 0, 1), (4, 5, 3), (2, 1, 7), (64, 20, 2))
 
 
 class Wfa2Adaptive:
@@ -90,6 +98,9 @@ def exact_answers(pairs, pens, cigar=False):
 #   long         8 pairs of 5 kbp at 10 % with a 150-base indel, under (10,10,1) and (64,20,1) by turns
 #   beyond16     2 pairs of 33.5 kbp at 0.5 %, under (10,50,1)
 #   small_default  the pairs of `small`, ALL under (10,10,1) and penalties (2,3,1)
+#   sweep        20 short pairs (endsfree_ref.sweep_pairs) per penalty set of SWEEP_PENS, pair i under SWEEP_HEUR[i % 5]; 5 long pairs
+#                (sweep_long) under each of SWEEP_LONG_PENS -- M rings of 8 and 66 rows, either side of the one-wave tier's limit --, one per
+#                heuristic
 def _planted(rng, n, rate, indel, insertion):
     p = rng.seq(n)
     cut = rng.integer(n // 4, 3 * n // 4)
@@ -103,7 +114,22 @@ def _planted(rng, n, rate, indel, insertion):
 def make_set(name):
     """-> (pairs, heuristics, pens) of a golden set."""
     pairs, heurs, pens = [], [], []
-    if name in ("small", ONE_SET):
+    if name == SWEEP_SET:
+        # The heuristic changes few answers of short related pairs: the unrelated pairs run to the full length here (they are where it
+        # bites), and the seed is the first after 20261004 under which WFA2's score lies above the optimum for ten pairs (MIN_DIFFERENT).
+        rng = Rng(20261005)
+        for j, pen in enumerate(SWEEP_PENS):
+            top = sweep_top(ring_depth(pen))
+            for i, pair in enumerate(sweep_pairs(rng, top, j, unrelated=top)):
+                pairs.append(pair)
+                heurs.append(SWEEP_HEUR[(i + j) % 5])
+                pens.append(pen)
+        for pen in SWEEP_LONG_PENS:
+            for i, pair in enumerate(sweep_long(rng)):
+                pairs.append(pair)
+                heurs.append(SWEEP_HEUR[i % 5])
+                pens.append(pen)
+    elif name in ("small", ONE_SET):
         rng = Rng(20260901)
         for i in range(400):
             if i == 9:
