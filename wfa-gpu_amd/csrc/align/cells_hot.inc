@@ -24,6 +24,12 @@
         // (round 5: the banded kernels too -- rows of 1024 diagonals on four waves, four chunks per wave and score: ONT-shaped 30 kbp
         // pairs 15.2 -> 14.8 ms; rows of 512 on two or four waves: within the noise)
         constexpr bool PAIRED = HYBRID || BANDED;
+        // The last chunk of a row stores under its lane mask instead of selecting NULL into the lanes beyond hi (three v_cndmask per
+        // score).  That needs the ring invariant on the upper side as the lower side has always needed it: both lean loops
+        // (loop_lean_e1.inc, loop_lean_any.inc; every exact LDS tier and the hybrid ring) keep it with clear_guards.  The banded loops
+        // (loop_banded.inc) store rows relative to a window that moves between scores and have no clear_guards; the argument has not
+        // been made for them: they stay with the selects.
+        constexpr bool MASKED_LAST = !BANDED;
         static_assert(TB >= (uint32_t)PER && (TB & (BT_M_MASK | BT_D_EXT | BT_I_EXT)) == 0, "tag base");
         // a group of up to four chunks from kq (this lane's diagonal; the lane base of every row involved is cell kq - 1:
         // all neighbours are immediates from there) and codes; returns whether the row goes on beyond the group
@@ -111,32 +117,55 @@
             constexpr int O = decltype(uc)::value * NT;
             constexpr bool PARTIAL = decltype(partial_tag)::value;
             if (__builtin_amdgcn_ballot_w64(c.more) != 0ull) {
-              uint32_t fb;
-              int togo = c.more ? max(c.rem - PER, 0) : 0;
-              while (__builtin_amdgcn_ballot_w64(togo > 0) != 0ull) {
-                c.pa += 4; c.ta += 4;
-                const LdsWords pw = (LdsWords)c.pa; const LdsWords tw = (LdsWords)c.ta;
-                const uint32_t d = __builtin_amdgcn_alignbit(pw[1], pw[0], c.sa) ^ __builtin_amdgcn_alignbit(tw[1], tw[0], c.sb);
-                asm("v_ffbl_b32 %0, %1" : "=v"(fb) : "v"(d));
-                const int nn = min(min((int)(fb >> BITS), PER), togo);
-                c.h += nn;
-                togo = (nn == PER) ? togo - PER : 0;
+              // The lanes whose run goes on (a whole word matched, bases left) stay in the loop, the others leave it through the
+              // execution mask: one back-edge, and no lane has to be kept inert.  togo = hmax - h of the lane while it is inside,
+              // so nothing but togo is carried: h follows from it when the lane leaves.  10 vector instructions and the two LDS
+              // reads per further word (a ballot loop with togo kept at 0 in the lanes that were done: 14 and three branches).
+              // (formed here, behind the branch: the full chunk does not pay for the test)
+              int togo = c.rem - PER;
+              asm volatile("" : "+v"(togo));
+              if (c.more && togo > 0) {
+                int m;
+                for (;;) {
+                  c.pa += 4; c.ta += 4;
+                  const LdsWords pw = (LdsWords)c.pa; const LdsWords tw = (LdsWords)c.ta;
+                  const uint32_t d = __builtin_amdgcn_alignbit(pw[1], pw[0], c.sa) ^ __builtin_amdgcn_alignbit(tw[1], tw[0], c.sb);
+                  uint32_t fb;
+                  asm("v_ffbl_b32 %0, %1" : "=v"(fb) : "v"(d));
+                  // (first mismatch or bases left, whichever is less; more than a word: the word matched and the run goes on)
+                  m = min((int)(fb >> BITS), togo);
+                  togo -= PER;      // (before the test: one register for togo, the last step is taken back below)
+                  asm volatile("" : "+v"(togo));      // (or the compiler keeps the value from before the step in a second one: a v_mov per word)
+                  if (m <= PER) break;
+                }
+                c.h = (c.hmax + m - PER) - togo;
               }
             }
-            int mv = c.h, ins_c = c.ins_c, del_t = c.del_t;
-            if constexpr (PARTIAL) {
+            auto stores = [&](const int mv, const int ins_c, const int del_t) {
+              w_m[O + 1] = (OffT)mv;
+              w_i[O + 1] = (OffT)(ins_c >> 16);     // (high halves: ds_write_b16_d16_hi, no unpacking)
+              w_d[O + 1] = (OffT)(del_t >> 16);
+              if constexpr (BT) {
+                // (a 32-bit sum: the store keeps its scalar base + 32-bit vector offset form for every chunk -- a 64-bit sum is a vector pair add)
+                if constexpr (TILED) codes[(size_t)(t_off + (uint32_t)(O * 4))] = (uint8_t)c.code;
+                else codes[O] = (uint8_t)c.code;
+              }
+            };
+            if constexpr (PARTIAL && MASKED_LAST) {
+              // The lanes beyond hi store nothing.  Their cells hold NULL already (the ring invariant: a row holds NULL outside the limits
+              // it was last written with -- a growing row's slot held a narrower row before, and once a limit can move inwards
+              // clear_guards NULLs the dm cells beyond each end), exactly what the cells below lo rely on, which no lane ever covers.
+              // (touch: a scalar, formed outside the masked part; the lanes beyond hi are taken out of it with the mask itself)
+              touch |= __builtin_amdgcn_ballot_w64(c.h == c.hmax) & act;
+              if (__builtin_amdgcn_inverse_ballot_w64(act)) stores(c.h, c.ins_c, c.del_t);
+            } else if constexpr (PARTIAL) {
               const bool active = __builtin_amdgcn_inverse_ballot_w64(act);
-              mv = active ? c.h : OffNull<OffT>::value;
-              ins_c = active ? ins_c : (int)0x80000000u; del_t = active ? del_t : (int)0x80000000u;
-            }
-            touch |= __builtin_amdgcn_ballot_w64(mv == c.hmax);      // (a NULL never equals it)
-            w_m[O + 1] = (OffT)mv;
-            w_i[O + 1] = (OffT)(ins_c >> 16);     // (high halves: ds_write_b16_d16_hi, no unpacking)
-            w_d[O + 1] = (OffT)(del_t >> 16);
-            if constexpr (BT) {
-              // (a 32-bit sum: the store keeps its scalar base + 32-bit vector offset form for every chunk -- a 64-bit sum is a vector pair add)
-              if constexpr (TILED) codes[(size_t)(t_off + (uint32_t)(O * 4))] = (uint8_t)c.code;
-              else codes[O] = (uint8_t)c.code;
+              const int mv = active ? c.h : OffNull<OffT>::value;
+              touch |= __builtin_amdgcn_ballot_w64(mv == c.hmax);      // (a NULL never equals it)
+              stores(mv, active ? c.ins_c : (int)0x80000000u, active ? c.del_t : (int)0x80000000u);
+            } else {
+              touch |= __builtin_amdgcn_ballot_w64(c.h == c.hmax);      // (a NULL never equals it)
+              stores(c.h, c.ins_c, c.del_t);
             }
           };
           auto chunk = [&](auto uc, auto partial_tag, const unsigned long long act) {

@@ -71,6 +71,7 @@
 #include <type_traits>
 
 #include "wfa_device.h"
+
 #include "pack_device.h"
 
 namespace {
@@ -528,8 +529,8 @@ wfa_align_kernel(const WfaAlignParams p) {
       };
       // ---- score 0: M[0][0] = extend(0) ------------------------------------------------------
       // (TILED) the alignment's block of tiles: 64-byte header {marker, wlo, tile columns, budget} + ((budget >> 2) + 1) groups of
-      // tile_cols tiles + four tiles of slack (the lanes of a row's last chunk beyond its upper limit store their bytes further right:
-      // into tiles of LATER scores of the block, which those scores overwrite, or into the slack)
+      // tile_cols tiles + four tiles of slack (from when the lanes of a row's last chunk beyond its upper limit stored their bytes
+      // further right; they store nothing now -- cells_hot.inc, MASKED_LAST -- and the block keeps its size)
       uint32_t tile_cols = 0;
       GlobalBytes tiles0 = nullptr;             // byte address of tile (0, 0)
       if constexpr (BT && TILED) {

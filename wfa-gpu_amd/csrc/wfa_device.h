@@ -98,10 +98,11 @@ enum : uint8_t { OP_X = 1, OP_I = 2, OP_D = 3, OP_EXT_AFTER = 0x10 };
 #define WFA_ROW_NONE 0xFFFFFFFFu
 constexpr unsigned long long WFA_ARENA_MAX_BYTES = (1ull << 36) - 4096;
 static_assert(WFA_ARENA_MAX_BYTES / 16 < WFA_ROW_NONE, "a row unit must never read as the TILES marker");
-// The lean cells of the 16-bit LDS tiers (0, 1, 2, 4) never switch a lane off: the lanes of a row's last 64-diagonal
+// The lean cells of the banded search never switch a lane off: the lanes of a row's last 64-diagonal
 // chunk that lie beyond its upper limit store NULL offsets into that many cells behind the row (every ring row carries
 // WFA_RING_ROW_PAD extra cells for it) and origin bytes behind the row's bytes in the arena (every arena chunk keeps
-// WFA_ARENA_ROW_SLACK 16-byte units unallocated at its end; the arena itself ends with 8 spare units).
+// WFA_ARENA_ROW_SLACK 16-byte units unallocated at its end; the arena itself ends with 8 spare units).  The exact lean loops
+// store that chunk under its lane mask (align/cells_hot.inc, MASKED_LAST) and write nothing beyond a row; pad and slack stay.
 #define WFA_RING_ROW_PAD 64
 #define WFA_ARENA_ROW_SLACK 4u
 
