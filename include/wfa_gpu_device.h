@@ -169,7 +169,8 @@ void wfagpu_amd_debug_times(const wfagpu_amd_ctx_t* ctx, const void** d_records,
 /* Diagnostics: which of the code objects that only some callers load this process has entered so far (launched, queried or
  * primed a kernel of) -- bit 0: the ends-free wavefront kernels, bit 1: the two-piece wavefront kernels, bit 2: the two-piece
  * backtrace kernels, bit 3: the wf-adaptive wavefront kernels, bit 4: the one-component (edit, indel, gap-linear) wavefront kernels,
- * bit 5: their backtrace kernels.  Process-wide, never cleared.  A gap-affine end-to-end caller reads 0. */
+ * bit 5: their backtrace kernels, bit 6: the one-component wavefront kernels under an ends-free span (only
+ * wfagpu_amd_align_device_linear_span with a span, or a metric configured with one, enters them).  Process-wide, never cleared.  A gap-affine end-to-end caller reads 0. */
 unsigned int wfagpu_amd_debug_code_objects(void);
 
 /* The HIP stream (hipStream_t) the context runs on -- its own, or the one given at creation. */
@@ -293,6 +294,23 @@ int wfagpu_amd_align_device_linear(wfagpu_amd_ctx_t* ctx, const wfagpu_amd_batch
  * again.  A bad member (as above), or a span, two-piece penalties or the wf-adaptive heuristic are configured: rejected (-1, message),
  * state unchanged -- as are those while a metric is configured. */
 int wfagpu_amd_configure_linear(const wfagpu_amd_linear_t* linear);
+
+/* A metric under an ends-free span: infix ("semi-global") edit, indel or gap-linear distance -- a barcode, primer or read found
+ * inside a longer text.  wfagpu_amd_align_device_linear with the span and d_ends of wfagpu_amd_align_device_span (same meaning, same
+ * clamping, k0 = INT32_MIN in score-only calls), on kernels of their own; scores and CIGARs are WFA2's under the metric with
+ * wavefront_aligner_set_alignment_free_ends, byte for byte: the free bases as D / I runs at the CIGAR's ends, priced for their
+ * paid bases alone.  span == NULL: wfagpu_amd_align_device_linear (d_ends is not written); a span of zeros: the same results.
+ * A negative member of the span or a bad metric (as above): -1, before any device work.  Exact, tiers as for the metric alone;
+ * not combined with a band, two pieces or the heuristic. */
+int wfagpu_amd_align_device_linear_span(wfagpu_amd_ctx_t* ctx, const wfagpu_amd_batch_t* batch, const wfagpu_amd_linear_t* linear, int max_error,
+                                        const wfagpu_amd_span_t* span, bool compute_cigar, int32_t* d_scores, int32_t* d_ends,
+                                        const char** d_text, const unsigned long long** d_off, const unsigned int** d_len);
+
+/* Process-wide: the metric of wfagpu_amd_configure_linear and its span, set together (span == NULL: end to end, which is what
+ * wfagpu_amd_configure_linear(linear) means).  linear == NULL clears both, as wfagpu_amd_configure_linear(NULL) does.  While a
+ * metric is configured by either call, wfagpu_amd_configure_span, _affine2p and _wfadaptive return -1 as before; while one of those
+ * three is configured, this call returns -1 and leaves the state alone.  A negative member or a bad metric: -1, state unchanged. */
+int wfagpu_amd_configure_linear_span(const wfagpu_amd_linear_t* linear, const wfagpu_amd_span_t* span);
 
 void wfagpu_amd_last_stats(const wfagpu_amd_ctx_t* ctx, wfagpu_amd_stats_t* out);
 

@@ -138,6 +138,7 @@ ABI_SYMBOLS = [
     "wfagpu_amd_align_device_2p", "wfagpu_amd_configure_affine2p", "wfagpu_amd_debug_code_objects",
     "wfagpu_amd_align_device_adaptive", "wfagpu_amd_configure_wfadaptive",
     "wfagpu_amd_align_device_linear", "wfagpu_amd_configure_linear",
+    "wfagpu_amd_align_device_linear_span", "wfagpu_amd_configure_linear_span",
 ]
 
 _lib = None
@@ -191,6 +192,12 @@ def load():
     lib.wfagpu_amd_align_device_linear.restype = C.c_int
     lib.wfagpu_amd_configure_linear.argtypes = [C.POINTER(Linear)]
     lib.wfagpu_amd_configure_linear.restype = C.c_int
+    lib.wfagpu_amd_align_device_linear_span.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Linear), C.c_int, C.POINTER(Span), C.c_bool,
+                                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                        C.POINTER(C.c_void_p)]
+    lib.wfagpu_amd_align_device_linear_span.restype = C.c_int
+    lib.wfagpu_amd_configure_linear_span.argtypes = [C.POINTER(Linear), C.POINTER(Span)]
+    lib.wfagpu_amd_configure_linear_span.restype = C.c_int
     lib.wfagpu_amd_debug_code_objects.argtypes = []
     lib.wfagpu_amd_debug_code_objects.restype = C.c_uint
     lib.wfagpu_amd_last_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
@@ -290,11 +297,16 @@ def configure_wfadaptive(heuristic=None):
         raise ValueError(f"wfagpu_amd_configure_wfadaptive rejected {tuple(heuristic)}")
 
 
-def configure_linear(linear=None):
+def configure_linear(linear=None, span=None):
     """wfagpu_amd_configure_linear: launch_alignments*, wfagpu_align and the CLI align under an edit, indel or gap-linear metric --
-    ("edit",), ("indel",) or ("linear", x, g) --; the gap-affine penalties they are handed are ignored.  None: gap-affine again.  Raises
+    ("edit",), ("indel",) or ("linear", x, g) --; the gap-affine penalties they are handed are ignored.  None: gap-affine again.
+    span (a Span, a dict of its fields or a 4-tuple; wfagpu_amd_configure_linear_span): the metric runs ends-free under it.  Raises
     ValueError when the library rejects it (a bad member, or a span, two-piece penalties or the heuristic are configured)."""
     lib = load()
+    if linear is not None and span is not None:
+        if lib.wfagpu_amd_configure_linear_span(C.byref(_as_linear(linear)), C.byref(_as_span(span))) != 0:
+            raise ValueError(f"wfagpu_amd_configure_linear_span rejected {tuple(linear)} under {span}")
+        return
     if linear is None:
         lib.wfagpu_amd_configure_linear(None)
         return
@@ -572,7 +584,8 @@ class DeviceAligner:
         wfadaptive: (min_wavefront_length, max_distance_threshold, steps_between_cutoffs), WFA2's wf-adaptive heuristic
         (wfagpu_amd_align_device_adaptive; end to end, gap-affine: a band, a span or two pieces is an error).
         linear: ("edit",), ("indel",) or ("linear", x, g), an edit, indel or gap-linear metric (wfagpu_amd_align_device_linear; exact
-        end-to-end search on one-component kernels: a band, a span, two pieces or the heuristic is an error); `penalties` is ignored then."""
+        search on one-component kernels: a band, two pieces or the heuristic is an error); `penalties` is ignored then.  With a span too:
+        the metric ends-free (wfagpu_amd_align_device_linear_span), fetch_ends as under a span alone."""
         torch = self.torch
         dev = torch.device("cuda", self.device)
         n = batch.num_pairs
@@ -586,8 +599,8 @@ class DeviceAligner:
             raise ValueError("two-piece penalties are not combined with an ends-free span or the adaptive band")
         if wfadaptive is not None and (span is not None or affine2p is not None or (band > 0 and band_width > 0)):
             raise ValueError("the wf-adaptive heuristic is not combined with an ends-free span, two-piece penalties or the adaptive band")
-        if linear is not None and (span is not None or affine2p is not None or wfadaptive is not None or (band > 0 and band_width > 0)):
-            raise ValueError("an edit, indel or gap-linear metric is not combined with a span, two-piece penalties, the heuristic or the adaptive band")
+        if linear is not None and (affine2p is not None or wfadaptive is not None or (band > 0 and band_width > 0)):
+            raise ValueError("an edit, indel or gap-linear metric is not combined with two-piece penalties, the heuristic or the adaptive band")
         d_ends = None
         if span is not None:
             if band > 0 and band_width > 0:
@@ -597,7 +610,11 @@ class DeviceAligner:
         elif fetch_ends:
             raise ValueError("fetch_ends needs a span")
         self._inputs_ready()
-        if linear is not None:
+        if linear is not None and span is not None:
+            rc = self.lib.wfagpu_amd_align_device_linear_span(self.ctx, C.byref(batch), C.byref(_as_linear(linear)), int(max_error), C.byref(span),
+                                                              bool(compute_cigar), d_scores.data_ptr(), d_ends.data_ptr() if d_ends is not None else None,
+                                                              C.byref(t), C.byref(o), C.byref(l))
+        elif linear is not None:
             rc = self.lib.wfagpu_amd_align_device_linear(self.ctx, C.byref(batch), C.byref(_as_linear(linear)), int(max_error),
                                                          bool(compute_cigar), d_scores.data_ptr(), C.byref(t), C.byref(o), C.byref(l))
         elif wfadaptive is not None:

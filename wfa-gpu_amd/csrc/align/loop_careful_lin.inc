@@ -11,6 +11,13 @@
 // Origin byte (ROWS in every tier): BTL_X / BTL_D / BTL_I by WFA2's priority on equal offsets (wavefront_backtrace.c:259-264).
 // Three reads and one store per cell; under indel two reads.
         ++s;
+        // (ENDSFREE: the reach interval surrounds an interval of end diagonals and outlives the budget by some scores: said here, the row
+        // table holds the scores up to the budget)
+        if constexpr (ENDSFREE) { if (s > budget) { status = WFA_ST_SCORE; break; } }
+        if constexpr (ENDSFREE && NW > 1) {
+          // word 0 of the reduction slot of the NEXT score (nobody reads it any more: its readers -- of score s-2 -- passed barrier s-1)
+          if (tid == 0) red[8 * ((s + 1) % 3)] = INT_MAX;
+        }
         if (reach_r == 0) { ++rlo; --rhi; reach_r = e - 1; } else --reach_r;
         const bool indel = x >= WFA_LIN_NO_MISMATCH;      // (wave-uniform: a kernel argument)
         p_m += rs;  if (p_m == m_end) p_m = m_first;
@@ -54,6 +61,10 @@
             out_m[q] = (OffT)OffNull<OffT>::value;
           }
         }
+        // (ENDSFREE) termination (wavefront_extend.c:124-170, 240-262): the LOWEST diagonal of the extended row whose cell has used up the
+        // text with at most pef pattern bases left, or the pattern with at most tef text bases left.  Every wave tests the cells it
+        // writes, as it writes them (the chunks ascend: its first hit is its lowest); NW > 1: the minimum over the waves below.
+        int my_end = INT_MAX;
         // ---- the cells of this score.  Lanes past the end recompute cell `hi` (same values, same addresses), so no store needs an exec
         // mask.  (x == g, and so edit: p_x and p_oe are the same row.)
         {
@@ -93,11 +104,33 @@
             const int mv = ok ? h : OffNull<OffT>::value;
             out_m[k] = (OffT)mv;
             if constexpr (BT) codes[(uint32_t)(k - lo)] = (uint8_t)code;
+            if constexpr (ENDSFREE) {
+              // (a cell that WFA2 trims holds NULL here: `ok` keeps it out)
+              const int vv = mv - k;
+              const bool hit = (k0 + tid <= hi) && ok && ((mv >= tlen && plen - vv <= pef) || (vv >= plen && tlen - mv <= tef));
+              const unsigned long long bh = __builtin_amdgcn_ballot_w64(hit);
+              if (bh && my_end == INT_MAX) my_end = k0 + (tid & ~63) + (int)__builtin_ctzll(bh);
+            }
           }
         }
+        if constexpr (ENDSFREE) {
+          // the one barrier of the score carries the minimum over the waves: word 0 of the score's reduction slot (three slots in
+          // rotation, reset two scores ahead: above)
+          if constexpr (NW == 1) {
+            block_sync<NW>();
+            end_k = my_end;
+          } else {
+            int* acc = red + 8 * (s % 3);
+            if (lane == 0 && my_end != INT_MAX) atomicMin(&acc[0], my_end);
+            __syncthreads();
+            end_k = acc[0];
+          }
+          done = end_k != INT_MAX;
+        } else {
         // termination (wavefront_extend.c:47-67): every lane reads the same cell, behind the one barrier of the score
         block_sync<NW>();
         done = ((unsigned)(kend - lo) <= (unsigned)(hi - lo)) && __builtin_amdgcn_readfirstlane((int)out_m[kend]) >= tlen;
+        }
         book.set(bk_s, pack_range(lo, hi), ROW_NONE_A, ROW_NONE_A);
         last_lo = lo; last_hi = hi;
         // (NW > 1: the book entry is a same-value store of every thread, each reads back its own)

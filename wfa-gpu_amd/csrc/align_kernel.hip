@@ -213,6 +213,9 @@ __device__ __forceinline__ ColdParams cold_params() {
 // ring of max(x, g) + 1 rows of M and nothing else (de == 0), no run-limit row, I / D entries of the row book never set; a score step
 // of its own with its cells (align/loop_careful_lin.inc: the careful one, WFA2 to the letter), origin bytes BTL_* in ROWS.  Window
 // and reach: below, where they are derived.
+// LINEAR && ENDSFREE (align_kernel_linef.hip includes this file for those instantiations): a one-component metric under a span -- the
+// start row and the epilogue of ENDSFREE on the M-only ring of LINEAR, the score step of LINEAR with the lowest-diagonal termination of
+// ENDSFREE, a window of its own (below).  DESIGN.md section 4.10.
 template <int NW, bool BT, typename OffT, bool GLOBAL_RING, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool TIMED = false, bool ENDSFREE = false,
           bool TWOPIECE = false, bool ADAPTIVE = false, bool LINEAR = false>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu((NW == 1 && !BANDED) ? WPE : 1, 8)))
@@ -221,7 +224,7 @@ wfa_align_kernel(const WfaAlignParams p) {
   static_assert(!ENDSFREE || (!BANDED && !HYBRID && !TIMED), "ends-free: the exact search of tiers 0, 1, 2 and 3");
   static_assert(!TWOPIECE || (!BANDED && !HYBRID && !TIMED && !ENDSFREE), "two pieces: the end-to-end exact search of tiers 0, 1, 2 and 3");
   static_assert(!ADAPTIVE || (!BANDED && !HYBRID && !TIMED && !ENDSFREE && !TWOPIECE), "wf-adaptive: end to end, gap-affine, tiers 0, 1, 2 and 3");
-  static_assert(!LINEAR || (!BANDED && !HYBRID && !TIMED && !ENDSFREE && !TWOPIECE && !ADAPTIVE), "one component: the end-to-end exact search of tiers 0, 1, 2 and 3");
+  static_assert(!LINEAR || (!BANDED && !HYBRID && !TIMED && !TWOPIECE && !ADAPTIVE), "one component: the exact search of tiers 0, 1, 2 and 3, end to end or ends-free");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NT = NW * 64;
   const int tid = threadIdx.x;
@@ -381,6 +384,23 @@ wfa_align_kernel(const WfaAlignParams p) {
       // base), so a ring of that many diagonals on either side of 0 holds every row up to the budget; the score step checks it.
       const long long kmax = budget >= oe ? ((long long)budget - (oe - e)) / e : 0;
       wlo = -(int)min((long long)plen, kmax); whi = (int)min((long long)tlen, kmax);
+    } else if constexpr (LINEAR && ENDSFREE) {
+      // One component under a span: a path starts on a diagonal a of S = [-pbf, tbf], ends on a diagonal b of E = [kend - tef, kend + pef]
+      // and moves by one diagonal per gap base.  One that visits a diagonal k above both holds at least (k - a) + (k - b) gap bases,
+      // fewest at a = tbf, b = kend + pef: 2 k - tbf - kend - pef <= S / g; below both, symmetric: -2 k - pbf - tef + kend <= S / g.
+      // Between the hulls' ends every diagonal stays (a quotient is taken of a non-negative numerator only).  feasible: the gap
+      // bases between the two intervals are affordable.  With a span of zeros these are the end-to-end formulas below:
+      // max(0, kend) + (gb - |kend|) / 2 = (gb + kend) / 2 and min(0, kend) - (gb - |kend|) / 2 = -((gb - kend) / 2) for either sign of kend.
+      const int s_lo = -pbf, s_hi = tbf, e_lo = kend - tef, e_hi = kend + pef;
+      const int H = max(s_hi, e_hi), L = min(s_lo, e_lo);
+      if (budget < INT_MAX / 2) {
+        const long long gb = budget / e;
+        feasible = (long long)max(0, max(e_lo - s_hi, s_lo - e_hi)) <= gb;
+        const long long a_hi = gb + s_hi + e_hi, a_lo = gb - s_lo - e_lo;
+        whi = a_hi >= 0 ? max(H, (int)min((long long)tlen, a_hi / 2)) : H;
+        wlo = a_lo >= 0 ? min(L, -(int)min((long long)plen, a_lo / 2)) : L;
+        whi = min(whi, tlen); wlo = max(wlo, -plen);
+      }
     } else if constexpr (LINEAR) {
       // One component, every gap base g.  A path moves by one diagonal per gap base, so one that visits a diagonal t beyond both 0 and
       // kend holds at least t + (t + |kend|) gap bases: g (2 t + |kend|) <= S.  The window is (S / g - |kend|) / 2 diagonals on either
@@ -779,7 +799,50 @@ int occ_inst(size_t lds) {
   return nb;
 }
 
-#if defined(WFA_ALIGN_LINEAR_UNIT)
+#if defined(WFA_ALIGN_LINEF_UNIT)
+// ---- the translation unit of the one-component metrics under a span (align_kernel_linef.hip): tiers 0, 1, 2 and 3, with and without
+// backtrace, packed and byte-compare
+template <bool BT, bool RAW>
+void launch_tier_linef(const WfaAlignParams& p, int tier, size_t lds, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  switch (tier) {
+    case 0: launch_inst<1, BT, int16_t, false, RAW, false, false, 8, false, true, false, false, true>(p, lds, grid, stream, ev0, ev1); break;
+    case 1: launch_inst<4, BT, int16_t, false, RAW, false, false, 8, false, true, false, false, true>(p, lds, grid, stream, ev0, ev1); break;
+    case 2: launch_inst<16, BT, int16_t, false, RAW, false, false, 8, false, true, false, false, true>(p, lds, grid, stream, ev0, ev1); break;
+    default:
+      if (p.ring16) launch_inst<16, BT, int16_t, true, RAW, false, false, 8, false, true, false, false, true>(p, lds, grid, stream, ev0, ev1);
+      else launch_inst<16, BT, int32_t, true, RAW, false, false, 8, false, true, false, false, true>(p, lds, grid, stream, ev0, ev1);
+      break;
+  }
+}
+template <bool BT, bool RAW>
+int occ_tier_linef(int tier, size_t lds) {
+  switch (tier) {
+    case 0: return occ_inst<1, BT, int16_t, false, RAW, false, false, 8, true, false, false, true>(lds);
+    case 1: return occ_inst<4, BT, int16_t, false, RAW, false, false, 8, true, false, false, true>(lds);
+    case 2: return occ_inst<16, BT, int16_t, false, RAW, false, false, 8, true, false, false, true>(lds);
+    default: return occ_inst<16, BT, int32_t, true, RAW, false, false, 8, true, false, false, true>(lds);
+  }
+}
+
+}  // namespace
+
+void wfa_launch_align_linef(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  wfa_unit_entered(WFA_UNIT_ALIGN_LINEF);
+  const size_t lds = wfa_align_lds_bytes(p, tier);
+  if (with_bt) { if (raw) launch_tier_linef<true, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_linef<true, false>(p, tier, lds, grid, stream, ev0, ev1); }
+  else { if (raw) launch_tier_linef<false, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_linef<false, false>(p, tier, lds, grid, stream, ev0, ev1); }
+}
+
+int wfa_align_linef_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds) {
+  wfa_unit_entered(WFA_UNIT_ALIGN_LINEF);
+  if (with_bt) return raw ? occ_tier_linef<true, true>(tier, lds) : occ_tier_linef<true, false>(tier, lds);
+  return raw ? occ_tier_linef<false, true>(tier, lds) : occ_tier_linef<false, false>(tier, lds);
+}
+
+// (this code object is loaded by the first launch of one of its kernels: wfagpu_amd_prime does that only under a metric configured with a span)
+namespace { __global__ void k_prime_align_linef() {} }
+void wfa_prime_align_linef(hipStream_t stream) { wfa_unit_entered(WFA_UNIT_ALIGN_LINEF); hipLaunchKernelGGL(k_prime_align_linef, dim3(1), dim3(64), 0, stream); }
+#elif defined(WFA_ALIGN_LINEAR_UNIT)
 // ---- the one-component translation unit (align_kernel_lin.hip): tiers 0, 1, 2 and 3, with and without backtrace, packed and byte-compare
 template <bool BT, bool RAW>
 void launch_tier_lin(const WfaAlignParams& p, int tier, size_t lds, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {

@@ -318,6 +318,12 @@ constexpr uint32_t OP_NONE = 0;
 // One component (WFA_TRACE_LINEAR_UNIT, trace_kernel_lin.hip, origin bytes BTL_*): the walk never leaves M -- score steps x and g
 // (carried as p.e), a run of matches may follow every operation (wavefront_backtrace.c:254-302).  On a border (v or h zero) the only
 // valid source is the gap along it, so the walk arrives at (0, 0) through the run WFA2 prints there (:275, 311-313).
+// Under a span (WfaTraceParams::ends; the kernels of align_kernel_linef.hip) WFA2 stops at v <= 0 || h <= 0 || score == 0 and prints
+// min(v, h) matches and the leading D / I run (:254-313); the walk reaches the same start.  A cell on a border with score > 0 can lie
+// on the traced path only beyond the free bases -- within them the row of score 0 holds a cell on its diagonal at no cost, and a
+// cheaper alignment would start there --, and beyond them its only valid source is the gap along the border (the mismatch and the
+// other gap would come from v < 0 or h < 0: NULL): the bytes lead along the border down to score 0, which is on the last free
+// diagonal, where walk_ended accepts it; the replay prints the free run, and the RLE sink merges the paid bases into it.
 __device__ __forceinline__ uint32_t walk_step(const uint32_t code, int& state, int& s, int& k, const WfaTraceParams& p) {
 #if defined(WFA_TRACE_LINEAR_UNIT)
   const uint32_t org = code & BTL_MASK;

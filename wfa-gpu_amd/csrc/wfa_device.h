@@ -298,6 +298,18 @@ void wfa_prime_align_lin(hipStream_t stream);
 // wfagpu_amd_align_device call to run under (nullptr: gap-affine), as three ints.
 bool wfa_configured_linear(int* out3);
 const int* wfa_lane_linear3();
+// The instantiations for a one-component metric under an ends-free span (align_kernel_linef.hip: a code object of their own, loaded
+// only by such calls): tiers 0, 1, 2 and 3, exact search, careful loop, origin bytes in ROWS; the one-component backtrace kernels
+// serve them as they are (the span travels in WfaTraceParams).  wfa_align_lds_bytes serves them too (WfaAlignParams::de == 0).
+void wfa_launch_align_linef(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream,
+                            hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+int wfa_align_linef_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds_bytes);
+void wfa_prime_align_linef(hipStream_t stream);
+// The span that wfagpu_amd_configure_linear_span set with its metric (wfa_launch.hip): false when the configured metric runs end to
+// end, or none is configured; out (optional) receives the four members.  wfa_lane_linear_span4: the span the calling thread -- a lane
+// of launch_alignments* -- wants its metric to run under (nullptr: end to end).
+bool wfa_configured_linear_span(int* out4);
+const int* wfa_lane_linear_span4();
 bool wfa_launch_trace(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);     // false: nothing to launch
 // (the backtrace of two-piece alignments: trace_kernel_2p.hip, the same kernels compiled for five walk states and BT2_* origin bytes)
 bool wfa_launch_trace_2p(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
@@ -321,7 +333,7 @@ const WfaShortEntry* wfa_short_entry_e4(int ascii, int bt, int l32, int idx);
 // Which of the optional code objects -- the ones only some callers load -- this process has entered: every host function that launches,
 // queries or primes a kernel of such a unit says so (the runtime loads a code object at the first of these).  Process-wide, never
 // cleared; wfagpu_amd_debug_code_objects() (wfa_host.hip) hands the bits out, tests check "never loaded" with them.
-enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u, WFA_UNIT_ALIGN_AD = 8u, WFA_UNIT_ALIGN_LIN = 16u, WFA_UNIT_TRACE_LIN = 32u };
+enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u, WFA_UNIT_ALIGN_AD = 8u, WFA_UNIT_ALIGN_LIN = 16u, WFA_UNIT_TRACE_LIN = 32u, WFA_UNIT_ALIGN_LINEF = 64u };
 void wfa_unit_entered(unsigned unit);
 // Code-object priming: one empty launch per kernel translation unit (see the definitions).
 void wfa_prime_pack(hipStream_t stream);

@@ -512,7 +512,11 @@ int wfagpu_amd_prime(wfagpu_amd_ctx_t* c) {
   if (wfa_configured_span(nullptr)) wfa_prime_align_ef(c->stream);      // (the ends-free kernels: only callers under a span load them)
   if (wfa_configured_affine2p(nullptr)) { wfa_prime_align_2p(c->stream); wfa_prime_trace_2p(c->stream); }  // (the two-piece kernels: only callers under such penalties)
   if (wfa_configured_wfadaptive(nullptr)) wfa_prime_align_ad(c->stream);      // (the wf-adaptive kernels: only callers under the heuristic)
-  if (wfa_configured_linear(nullptr)) { wfa_prime_align_lin(c->stream); wfa_prime_trace_lin(c->stream); }  // (the one-component kernels: only callers under such a metric)
+  // (the one-component kernels: only callers under such a metric -- the ends-free ones where it was configured with a span)
+  if (wfa_configured_linear(nullptr)) {
+    if (wfa_configured_linear_span(nullptr)) wfa_prime_align_linef(c->stream); else wfa_prime_align_lin(c->stream);
+    wfa_prime_trace_lin(c->stream);
+  }
   LAUNCH_K(k_iota, dim3(1), dim3(64), 0, c->stream, static_cast<uint32_t*>(nullptr), 0u, 0u);      // (this file's)
   HIP_TRY(hipGetLastError());
   c->primed = true;
@@ -614,6 +618,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   // One component (p.de == 0: edit, indel, gap-linear): tiers 0, 1, 2 and 3 likewise.  Its window -- (S / g - |kend|) / 2 diagonals on
   // either side of the end diagonals -- is widest at |kend| = S / g: S / g + 1 diagonals, which is window_width with o = 0; its ring is
   // dm rows and nothing else (de == 0), which wfa_align_lds_bytes sees: a pair that needs four waves under gap-affine may fit one here.
+  // One component under a span (p.de == 0 and p.ends: align_kernel_linef.hip): that bound widened by the free bases, as for the gap-affine span.
   const bool ef = p.ends != nullptr, tp2 = p.e2 > 0, ad = p.ad_steps > 0, lin = p.de == 0;
   int width = ad ? window_width_ad(max_score, p.oe - p.e, p.e, max_seq_len) : tp2 ? window_width_2p(max_score, p, max_seq_len) : window_width(max_score, p.oe - p.e, p.e, max_seq_len);
   if (ef) {
@@ -652,7 +657,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     if (t == 0 && (width > 1024 || p.dm > 64)) continue;
     if (t == 1 && width > 8192) continue;
     if (t == 1 && few_pairs && width >= 1024 && !min_tier && wfa_align_lds_bytes(p, 2) <= budget[2]) continue;
-    int nb = lin ? wfa_align_lin_max_blocks_per_cu(t, bt, raw, lds) : ad ? wfa_align_ad_max_blocks_per_cu(t, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(t, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(t, bt, raw, lds) : wfa_align_max_blocks_per_cu(t, bt, raw, false, lds);
+    int nb = (lin && ef) ? wfa_align_linef_max_blocks_per_cu(t, bt, raw, lds) : lin ? wfa_align_lin_max_blocks_per_cu(t, bt, raw, lds) : ad ? wfa_align_ad_max_blocks_per_cu(t, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(t, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(t, bt, raw, lds) : wfa_align_max_blocks_per_cu(t, bt, raw, false, lds);
     if (nb < 1) continue;
     // Occupancy-matched instantiation of the one-wave kernels: LDS decides how many rings a CU holds; compiled for 8 waves
     // per SIMD the kernel lives on 64 VGPRs and 78 SGPRs (123 scalar spills + scratch), which only pays when 8 waves per
@@ -696,7 +701,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   p.rs = rs_plain;
   const size_t lds = wfa_align_lds_bytes(p, 3);
   if (lds > c->lds_per_block_max) return false;   // sequences themselves do not fit LDS
-  const int nb = lin ? wfa_align_lin_max_blocks_per_cu(3, bt, raw, lds) : ad ? wfa_align_ad_max_blocks_per_cu(3, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(3, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(3, bt, raw, lds) : wfa_align_max_blocks_per_cu(3, bt, raw, false, lds);
+  const int nb = (lin && ef) ? wfa_align_linef_max_blocks_per_cu(3, bt, raw, lds) : lin ? wfa_align_lin_max_blocks_per_cu(3, bt, raw, lds) : ad ? wfa_align_ad_max_blocks_per_cu(3, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(3, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(3, bt, raw, lds) : wfa_align_max_blocks_per_cu(3, bt, raw, false, lds);
   *out = {3, width, max_score, lds, std::max(1, std::min(nb, 2))};
   return true;
 }
@@ -731,12 +736,13 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
                              const wfagpu_amd_penalties2p_t* pen2 = nullptr, const wfagpu_amd_wfadaptive_t* wfad = nullptr,
                              const wfagpu_amd_linear_t* linm = nullptr) {
   if (!c || !b || !d_scores) return -1;
-  // linm != nullptr: an edit, indel or gap-linear metric (align_kernel_lin.hip: one component), exact search, end to end; `pen` is ignored:
+  // linm != nullptr: an edit, indel or gap-linear metric (align_kernel_lin.hip: one component), exact search, end to end -- or, with a
+  // span, ends-free (align_kernel_linef.hip: the two are combined through wfagpu_amd_align_device_linear_span alone); `pen` is ignored:
   // it becomes (x, 0, g) -- a gap base costs g, nothing opens -- for everything below that only sizes or bounds; indel: x = 2 g, what an
   // insertion and a deletion in place of a mismatch cost (the kernel gets ap.x = WFA_LIN_NO_MISMATCH: no mismatch move)
   const bool lin = linm != nullptr;
   if (lin) {
-    if (span || pen2 || wfad) { fprintf(stderr, "[!] ERROR: an edit, indel or gap-linear metric is not combined with a span, two-piece penalties or the wf-adaptive heuristic\n"); return -1; }
+    if (pen2 || wfad) { fprintf(stderr, "[!] ERROR: an edit, indel or gap-linear metric is not combined with two-piece penalties or the wf-adaptive heuristic\n"); return -1; }
     if (linm->metric == WFAGPU_AMD_METRIC_EDIT) { pen.x = 1; pen.e = 1; }
     else if (linm->metric == WFAGPU_AMD_METRIC_INDEL) { pen.x = 2; pen.e = 1; }
     else if (linm->metric == WFAGPU_AMD_METRIC_GAP_LINEAR && linm->mismatch > 0 && linm->indel > 0) { pen.x = linm->mismatch; pen.e = linm->indel; }
@@ -1194,6 +1200,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
           // (with CIGARs the launch owns n_cur slots above the bump pointer: move it past them for whatever allocates next)
           if (cigar_now && !ap.arena_top_known) LAUNCH_K(k_bump, dim3(1), dim3(64), 0, st, ap.arena_top, (unsigned long long)n_cur * wfa_short_bt_slot_units(ap.max_score, tp.wpe), ap.arena_units);
         }
+        else if (lin && ef) wfa_launch_align_linef(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else if (ef) wfa_launch_align_ef(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else if (tp2) wfa_launch_align_2p(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else if (ad) wfa_launch_align_ad(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
@@ -1670,6 +1677,12 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
   const int* const ll = wfa_lane_linear3();
   if (ll) {
     const wfagpu_amd_linear_t lm{ll[0], ll[1], ll[2]};
+    // (configured with a span -- wfagpu_amd_configure_linear_span --: the lane hands that over too)
+    const int* const lsp = wfa_lane_linear_span4();
+    if (lsp) {
+      const wfagpu_amd_span_t span{lsp[0], lsp[1], lsp[2], lsp[3]};
+      return align_device_impl(c, b, affine_penalties_t{}, max_error, -1, 0, compute_cigar, d_scores, d_text, d_off, d_len, &span, nullptr, nullptr, nullptr, &lm);
+    }
     return align_device_impl(c, b, affine_penalties_t{}, max_error, -1, 0, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, nullptr, nullptr, &lm);
   }
   // (and for a configured wf-adaptive heuristic: wfagpu_amd_configure_wfadaptive)
@@ -1693,6 +1706,15 @@ extern "C" int wfagpu_amd_align_device_linear(wfagpu_amd_ctx_t* c, const wfagpu_
                                               const unsigned int** d_len) {
   if (!linear) { fprintf(stderr, "[!] ERROR: wfagpu_amd_align_device_linear needs a metric\n"); return -1; }
   return align_device_impl(c, b, affine_penalties_t{}, max_error, -1, 0, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, nullptr, nullptr, linear);
+}
+
+extern "C" int wfagpu_amd_align_device_linear_span(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b, const wfagpu_amd_linear_t* linear, int max_error,
+                                                   const wfagpu_amd_span_t* span, bool compute_cigar, int32_t* d_scores, int32_t* d_ends,
+                                                   const char** d_text, const unsigned long long** d_off, const unsigned int** d_len) {
+  if (!linear) { fprintf(stderr, "[!] ERROR: wfagpu_amd_align_device_linear_span needs a metric\n"); return -1; }
+  // (NULL: the end-to-end kernels, d_ends is left alone.  A span of zeros runs the ends-free kernels -- a start row of one cell, one
+  // end diagonal, the end-to-end window -- and gives the same bytes.)
+  return align_device_impl(c, b, affine_penalties_t{}, max_error, -1, 0, compute_cigar, d_scores, d_text, d_off, d_len, span, span ? d_ends : nullptr, nullptr, nullptr, linear);
 }
 
 extern "C" int wfagpu_amd_align_device_2p(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b, const wfagpu_amd_penalties2p_t* pens, int max_error,

@@ -66,6 +66,11 @@ thread_local const int* t_lane_ad = nullptr;
 bool g_lin_set = false;
 int g_lin[3] = {0, 0, 0};
 thread_local const int* t_lane_lin = nullptr;
+// The span a metric was configured with (wfagpu_amd_configure_linear_span): part of the metric's state -- set and cleared with it,
+// never g_span, which stays the gap-affine span's -- and handed over the same way (wfa_lane_linear_span4).
+bool g_lin_span_set = false;
+int g_lin_span[4] = {0, 0, 0, 0};
+thread_local const int* t_lane_lin_span = nullptr;
 }  // namespace
 
 bool wfa_configured_linear(int* out3) {
@@ -74,11 +79,24 @@ bool wfa_configured_linear(int* out3) {
   return g_lin_set;
 }
 const int* wfa_lane_linear3() { return t_lane_lin; }
+bool wfa_configured_linear_span(int* out4) {
+  std::lock_guard<std::mutex> lock(g_span_mutex);
+  const bool set = g_lin_set && g_lin_span_set;
+  if (out4 && set) for (int i = 0; i < 4; ++i) out4[i] = g_lin_span[i];
+  return set;
+}
+const int* wfa_lane_linear_span4() { return t_lane_lin_span; }
 
-extern "C" int wfagpu_amd_configure_linear(const wfagpu_amd_linear_t* m) {
+// (one body for wfagpu_amd_configure_linear -- sp == nullptr: this metric end to end -- and wfagpu_amd_configure_linear_span)
+static int configure_linear_impl(const wfagpu_amd_linear_t* m, const wfagpu_amd_span_t* sp) {
   if (m && !(m->metric == WFAGPU_AMD_METRIC_INDEL || m->metric == WFAGPU_AMD_METRIC_EDIT ||
              (m->metric == WFAGPU_AMD_METRIC_GAP_LINEAR && m->mismatch > 0 && m->indel > 0))) {
     fprintf(stderr, "[!] ERROR: a metric is indel (0), edit (1) or gap-linear (2) with mismatch > 0 and indel > 0 (got %d,%d,%d)\n", m->metric, m->mismatch, m->indel);
+    return -1;
+  }
+  if (m && sp && (sp->pattern_begin_free < 0 || sp->pattern_end_free < 0 || sp->text_begin_free < 0 || sp->text_end_free < 0)) {
+    fprintf(stderr, "[!] ERROR: the members of a span must not be negative (got %d,%d,%d,%d)\n", sp->pattern_begin_free, sp->pattern_end_free,
+            sp->text_begin_free, sp->text_end_free);
     return -1;
   }
   std::lock_guard<std::mutex> lock(g_span_mutex);
@@ -89,8 +107,14 @@ extern "C" int wfagpu_amd_configure_linear(const wfagpu_amd_linear_t* m) {
   }
   g_lin_set = m != nullptr;
   if (m) { g_lin[0] = m->metric; g_lin[1] = m->mismatch; g_lin[2] = m->indel; }
+  // (the metric's span goes with it: NULL metric or NULL span -- end to end)
+  g_lin_span_set = m != nullptr && sp != nullptr;
+  if (g_lin_span_set) { g_lin_span[0] = sp->pattern_begin_free; g_lin_span[1] = sp->pattern_end_free; g_lin_span[2] = sp->text_begin_free; g_lin_span[3] = sp->text_end_free; }
   return 0;
 }
+
+extern "C" int wfagpu_amd_configure_linear(const wfagpu_amd_linear_t* m) { return configure_linear_impl(m, nullptr); }
+extern "C" int wfagpu_amd_configure_linear_span(const wfagpu_amd_linear_t* m, const wfagpu_amd_span_t* span) { return configure_linear_impl(m, span); }
 
 bool wfa_configured_wfadaptive(int* out3) {
   std::lock_guard<std::mutex> lock(g_span_mutex);
@@ -318,6 +342,10 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
   // score checked against the one-table program; the penalties of the options are not looked at)
   int m3[3] = {0, 0, 0};
   const int* const lm = wfa_configured_linear(m3) ? m3 : nullptr;
+  // (a metric configured with a span: the text priced under the metric without its free runs, the score checked against the
+  // one-table program with free borders)
+  int ls4[4] = {0, 0, 0, 0};
+  const int* const lspan = (lm && wfa_configured_linear_span(ls4)) ? ls4 : nullptr;
   std::atomic<long> above{0};
   std::atomic<long long> excess{0};
   auto worker = [&](unsigned) {
@@ -335,7 +363,8 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
         if (a.cigar) {
           const char* cg = a.results[i].cigar.buffer;
           const bool c1 = check_cigar_edit(text, pattern, m.text_len, m.pattern_len, cg);
-          const bool c2 = lm ? check_linear_distance(text, pattern, m.text_len, m.pattern_len, dist, lm[0], lm[1], lm[2], cg)
+          const bool c2 = lspan ? check_linear_distance_span(text, pattern, m.text_len, m.pattern_len, dist, lm[0], lm[1], lm[2], cg, lspan)
+                        : lm ? check_linear_distance(text, pattern, m.text_len, m.pattern_len, dist, lm[0], lm[1], lm[2], cg)
                         : p2 ? check_affine2p_distance(text, pattern, m.text_len, m.pattern_len, dist, p2[0], p2[1], p2[2], p2[3], p2[4], cg)
                         : span ? check_affine_distance_span(text, pattern, m.text_len, m.pattern_len, dist, a.opt.penalties.x,
                                                             a.opt.penalties.o, a.opt.penalties.e, cg, span)
@@ -344,7 +373,8 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
           if (!c1) LOG_ERROR("Incorrect cigar (%ld). Distance: %d. CIGAR: %s", i, dist, cg);
           ok = c1 && c2;
         }
-        const int cpu = lm ? verification_cpu_score_linear(pattern, text, m.pattern_len, m.text_len, lm[0], lm[1], lm[2])
+        const int cpu = lspan ? verification_cpu_score_linear_span(pattern, text, m.pattern_len, m.text_len, lm[0], lm[1], lm[2], lspan)
+                      : lm ? verification_cpu_score_linear(pattern, text, m.pattern_len, m.text_len, lm[0], lm[1], lm[2])
                       : p2 ? verification_cpu_score_2p_scratch(pattern, text, m.pattern_len, m.text_len, p2[0], p2[1], p2[2], p2[3], p2[4], &scratch)
                       : span ? verification_cpu_score_span_scratch(pattern, text, m.pattern_len, m.text_len, a.opt.penalties.x,
                                                                    a.opt.penalties.o, a.opt.penalties.e, span, &scratch)
@@ -1074,12 +1104,15 @@ int run_device(const CallArgs& a, Shard& sh) {
                                              (a.opt.band > 0 && a.opt.threads_per_block > 0) ? " and the adaptive band" : "");
       }
       t_lane_lin = under_lin ? m3 : nullptr;
+      int ms4[4];
+      t_lane_lin_span = (under_lin && wfa_configured_linear_span(ms4)) ? ms4 : nullptr;
       const int arc = wfagpu_amd_align_device(L.ctx, &wb, a.opt.penalties, a.opt.max_error, a.opt.band, a.opt.threads_per_block, a.cigar,
                                               d_sc, &bo.d_text, &bo.d_off, &bo.d_len);
       t_lane_span = nullptr;
       t_lane_2p = nullptr;
       t_lane_ad = nullptr;
       t_lane_lin = nullptr;
+      t_lane_lin_span = nullptr;
       if (arc) return arc;
       bo.d_scores = d_sc;
       if (a.cigar) { wfagpu_amd_stats_t stt; wfagpu_amd_last_stats(L.ctx, &stt); bo.text_bytes = stt.text_bytes; }

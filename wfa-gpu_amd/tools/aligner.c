@@ -15,6 +15,7 @@
 #include "../../include/wfa_gpu_device.h"
 #include "../utils/logger.h"
 #include "../utils/sequence_reader.h"
+#include "../utils/span_arg.h"
 #include "../utils/wf_clock.h"
 
 /* The first device query of a process initialises the HIP runtime (0.2-0.3 s) and starts bringing the device up in the background
@@ -67,6 +68,8 @@ static void usage(const char* prog) {
            "\t    --indel                       Indel (LCS) distance: gap base 1 and no mismatches (no X in a CIGAR)\n"
            "\t    --gap-linear <x,g>            Gap-linear penalties: mismatch x, every gap base g\n"
            "\t                                  (each of the three: not with another, -g, -B, --ends-free, --affine2p or --wfa-adaptive)\n"
+           "\t    --metric-ends-free <pb,pe,tb,te> --edit, --indel or --gap-linear under an ends-free span (the members as for --ends-free):\n"
+           "\t                                  only together with one of the three; not with -B, --ends-free, --affine2p or --wfa-adaptive\n"
            "[System]\n"
            "\t-t, --threads-per-block <int>     Accepted for compatibility (band width in banded mode)\n"
            "\t-w, --workers <int>               Accepted for compatibility\n"
@@ -91,7 +94,7 @@ int main(int argc, char** argv) {
         {"workers", required_argument, 0, 'w'}, {"help", no_argument, 0, 'h'}, {"stage-times", no_argument, 0, 1000},
         {"ends-free", required_argument, 0, 1001}, {"affine2p", required_argument, 0, 1002},
         {"wfa-adaptive", required_argument, 0, 1003}, {"edit", no_argument, 0, 1004}, {"indel", no_argument, 0, 1005},
-        {"gap-linear", required_argument, 0, 1006}, {0, 0, 0, 0}};
+        {"gap-linear", required_argument, 0, 1006}, {"metric-ends-free", required_argument, 0, 1007}, {0, 0, 0, 0}};
     const char *seq_path = NULL, *q_path = NULL, *t_path = NULL, *out_path = NULL, *pen_str = NULL;
     long n_read = 0, max_distance = -1, batch_size = -1, band_arg = -2, tpb = -1, workers = -1;
     bool print_out = false, verbose = false, cigar = false, check = false, stage_times = false;
@@ -99,6 +102,7 @@ int main(int argc, char** argv) {
     const char* pen2_str = NULL;
     const char* wfad_str = NULL;
     const char* lin_str = NULL;
+    const char* mspan_str = NULL;
     int n_metric = 0, metric = -1;
 
 
@@ -128,6 +132,7 @@ int main(int argc, char** argv) {
             case 1004: metric = WFAGPU_AMD_METRIC_EDIT; ++n_metric; break;      /* (not in the reference: WFA2's edit, indel and gap_linear metrics) */
             case 1005: metric = WFAGPU_AMD_METRIC_INDEL; ++n_metric; break;
             case 1006: metric = WFAGPU_AMD_METRIC_GAP_LINEAR; lin_str = optarg; ++n_metric; break;
+            case 1007: mspan_str = optarg; break;      /* (not in the reference: a metric under WFA2's ends-free alignment) */
             case 'h': usage(argv[0]); exit(0);
             default: break;      /* an option the tool does not know is skipped, like the reference's parser does (utils/arg_handler.c:97-140) */
         }
@@ -138,6 +143,27 @@ int main(int argc, char** argv) {
         return 1;
     }
 
+    /* --metric-ends-free: four non-negative integers, nothing behind them; only together with exactly one of --edit, --indel and
+     * --gap-linear, not together with -B, --ends-free, --affine2p or --wfa-adaptive.  Checked first of all, and like the others before
+     * any device work; the metric's own block below configures the two together. */
+    int mspan4[4] = {0, 0, 0, 0};
+    if (mspan_str) {
+        if (!span_arg_parse(mspan_str, mspan4)) {
+            LOG_ERROR("--metric-ends-free takes four non-negative integers pb,pe,tb,te (got \"%s\").", mspan_str)
+            usage(argv[0]);
+            return 1;
+        }
+        if (n_metric != 1) {
+            LOG_ERROR("--metric-ends-free is the span of a metric: it goes together with one of --edit, --indel and --gap-linear.")
+            usage(argv[0]);
+            return 1;
+        }
+        if (band_arg != -2 || span_str || pen2_str || wfad_str) {
+            LOG_ERROR("--metric-ends-free is an exact search under a metric: it is not combined with -B, --ends-free, --affine2p or --wfa-adaptive.")
+            usage(argv[0]);
+            return 1;
+        }
+    }
     /* --ends-free: four non-negative integers, nothing behind them; not together with the adaptive band.  Checked before any
      * device work: the device query thread starts below. */
     if (span_str) {
@@ -214,6 +240,11 @@ int main(int argc, char** argv) {
             usage(argv[0]);
             return 1;
         }
+        if (mspan_str) {
+            const wfagpu_amd_span_t mspan = {mspan4[0], mspan4[1], mspan4[2], mspan4[3]};
+            if (wfagpu_amd_configure_linear_span(&lin, &mspan) != 0) return 1;
+            LOG_INFO("Ends-free under the metric: pattern begin/end free %d/%d, text begin/end free %d/%d.", mspan4[0], mspan4[1], mspan4[2], mspan4[3])
+        } else
         if (wfagpu_amd_configure_linear(&lin) != 0) return 1;
         if (metric == WFAGPU_AMD_METRIC_GAP_LINEAR) LOG_INFO("Gap-linear penalties: M=0, X=%d, gap base %d.", lin.mismatch, lin.indel)
         else LOG_INFO("%s distance.", metric == WFAGPU_AMD_METRIC_EDIT ? "Edit" : "Indel")

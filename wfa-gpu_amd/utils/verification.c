@@ -434,3 +434,75 @@ int verification_cpu_score_linear(const char* pattern, const char* text, size_t 
     free(rows);
     return s;
 }
+
+/* ---- a one-component metric under an ends-free span (see verification.h) ---- */
+bool check_linear_distance_span(const char* text, const char* pattern, size_t tlen, size_t plen,
+                                int distance, int metric, int x, int g, const char* cigar, const int* span) {
+    (void)text; (void)pattern;
+    if (!linear_pens(metric, &x, &g)) return false;
+    int pb, pe, tb, te;
+    clamp_span(span, (int)plen, (int)tlen, &pb, &pe, &tb, &te);
+    /* items first: the last one is only known at the end */
+    size_t n_items = 0;
+    for (const char* c = cigar; *c;) { long n; char op; c = next_item(c, &n, &op); if (!c) return false; ++n_items; }
+    long cost = 0;
+    size_t idx = 0;
+    const char* c = cigar;
+    while (*c) {
+        long n = 0; char op = 0;
+        c = next_item(c, &n, &op);      /* (well-formed: checked above) */
+        if (op == 'I' || op == 'D') {
+            long paid = n;
+            if (idx == 0) { const long f = op == 'I' ? tb : pb; paid -= f < paid ? f : paid; }
+            if (idx + 1 == n_items) { const long f = op == 'I' ? te : pe; paid -= f < paid ? f : paid; }
+            cost += paid * g;
+        } else if (op == 'X') { if (x == 0) return false; cost += n * x; }      /* (indel: an X is a failure) */
+        else if (op != 'M') return false;
+        ++idx;
+    }
+    return cost == distance;
+}
+
+/* The program of verification_cpu_score_linear with free borders: score 0 holds every diagonal of [-pbf, tbf] at offset max(k, 0);
+ * the alignment ends with the first score one of whose cells has used up the text with at most pef pattern bases left, or the
+ * pattern with at most tef text bases left. */
+int verification_cpu_score_linear_span(const char* pattern, const char* text, size_t plen_, size_t tlen_, int metric, int x, int g, const int* span) {
+    if (!linear_pens(metric, &x, &g)) return -1;
+    const int plen = (int)plen_, tlen = (int)tlen_, kend = tlen - plen;
+    int pbf, pef, tbf, tef;
+    clamp_span(span, plen, tlen, &pbf, &pef, &tbf, &tef);
+    const int W = plen + tlen + 3, K0 = plen + 1, depth = (x > g ? x : g) + 1, NONE = -(1 << 29);
+    int* rows = (int*)malloc((size_t)depth * W * sizeof(int));
+    if (!rows) return -1;
+    for (long i = 0; i < (long)depth * W; ++i) rows[i] = NONE;
+    bool ended = false;
+    for (int k = -pbf; k <= tbf; ++k) {
+        int h = k > 0 ? k : 0, v = h - k;
+        while (h < tlen && v < plen && pattern[v] == text[h]) { ++h; ++v; }
+        rows[K0 + k] = h;
+        if ((h >= tlen && plen - v <= pef) || (v >= plen && tlen - h <= tef)) ended = true;
+    }
+    int s = 0;
+    /* (the end-to-end alignment is a candidate: no ends-free one costs more) */
+    const long worst = (long)2 * g * (plen < tlen ? plen : tlen) + (long)g * (kend < 0 ? -kend : kend);
+    while (!ended) {
+        ++s;
+        if (s > worst) { s = -1; break; }
+        int* cur = rows + (size_t)(s % depth) * W;
+        const int* rg = s >= g ? rows + (size_t)((s - g) % depth) * W : NULL;
+        const int* rx = (x > 0 && s >= x) ? rows + (size_t)((s - x) % depth) * W : NULL;
+        for (int k = -plen; k <= tlen; ++k) {
+            int best = NONE;
+            if (rx && rx[K0 + k] + 1 > best) best = rx[K0 + k] + 1;
+            if (rg && rg[K0 + k - 1] + 1 > best) best = rg[K0 + k - 1] + 1;
+            if (rg && rg[K0 + k + 1] > best) best = rg[K0 + k + 1];
+            int h = best, v = best - k;
+            if (h < 0 || v < 0 || h > tlen || v > plen) { cur[K0 + k] = NONE; continue; }
+            while (h < tlen && v < plen && pattern[v] == text[h]) { ++h; ++v; }
+            cur[K0 + k] = h;
+            if ((h >= tlen && plen - v <= pef) || (v >= plen && tlen - h <= tef)) ended = true;
+        }
+    }
+    free(rows);
+    return s;
+}

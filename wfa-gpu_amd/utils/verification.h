@@ -71,6 +71,14 @@ bool check_linear_distance(const char* text, const char* pattern, size_t tlen, s
                            int distance, int metric, int x, int g, const char* cigar);
 int verification_cpu_score_linear(const char* pattern, const char* text, size_t plen, size_t tlen, int metric, int x, int g);
 
+/* A one-component metric under an ends-free span (wfagpu_amd_align_device_linear_span, --metric-ends-free): span as above.  The CIGAR
+ * is priced under the metric WITHOUT its free bases -- a leading D (I) run is free for as many bases as pattern_begin_free
+ * (text_begin_free) allows, a trailing one for pattern_end_free (text_end_free); an X under indel is a failure --, the score checked
+ * against the one-table scalar program with free borders. */
+bool check_linear_distance_span(const char* text, const char* pattern, size_t tlen, size_t plen,
+                                int distance, int metric, int x, int g, const char* cigar, const int* span);
+int verification_cpu_score_linear_span(const char* pattern, const char* text, size_t plen, size_t tlen, int metric, int x, int g, const int* span);
+
 #ifdef __cplusplus
 }
 #endif
