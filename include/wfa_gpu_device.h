@@ -32,7 +32,8 @@ typedef struct {
     int max_blocks_per_cu; /* occupancy experiments: cap on resident workgroups per CU (0: none)                         */
     int t0_min_blocks;     /* one-wave tier only while LDS leaves at least this many rings per CU (0: default, 10)       */
     int waves_per_simd;    /* one-wave exact kernels: force the instantiation compiled for 8, 7, 6 or 4 waves per SIMD
-                              (0: matched to the rings LDS lets a CU hold)                                               */
+                              (0: matched to the rings LDS lets a CU hold); tier 5 under a metric: 16 or 32 = at least that
+                              many lanes per alignment (A/B of the 8- and 16-lane groups)                                */
     int trace_mode;        /* 0: automatic; 1: lane-per-alignment walk + windowed emit whatever the length (the fallback
                               of the wave-per-alignment kernel); 2: the wave-per-alignment kernel does the whole backtrace
                               (never several alignments per wavefront, never walk there + replay in the lane kernel); 3: never
@@ -121,7 +122,9 @@ typedef struct {
     unsigned long long arena_units;    /* 16-byte units of backtrace arena used           */
     unsigned long long text_bytes;     /* CIGAR text bytes produced                       */
     unsigned int pairs_tier[6];        /* pairs finished per kernel tier (0: 1 wave, 1: 4 waves, 2: 16 waves, 3: HBM ring, 4: hybrid ring,
-                                          5: short wavefronts -- several alignments per wave, score-only)                      */
+                                          5: short wavefronts -- several alignments per wave; gap-affine, and edit, indel and
+                                             gap-linear where the caller's max_error makes the diagonal window fit 32 lanes;
+                                             score-only and with CIGARs)                                                         */
     unsigned int pairs_retried;        /* pairs that needed a wider tier                  */
     unsigned int pairs_raw;            /* pairs with bytes outside ACGT (byte-compare kernels) */
     unsigned int pairs_banded;         /* pairs finished by the adaptive-band kernels          */
@@ -170,7 +173,9 @@ void wfagpu_amd_debug_times(const wfagpu_amd_ctx_t* ctx, const void** d_records,
  * primed a kernel of) -- bit 0: the ends-free wavefront kernels, bit 1: the two-piece wavefront kernels, bit 2: the two-piece
  * backtrace kernels, bit 3: the wf-adaptive wavefront kernels, bit 4: the one-component (edit, indel, gap-linear) wavefront kernels,
  * bit 5: their backtrace kernels, bit 6: the one-component wavefront kernels under an ends-free span (only
- * wfagpu_amd_align_device_linear_span with a span, or a metric configured with one, enters them).  Process-wide, never cleared.  A gap-affine end-to-end caller reads 0. */
+ * wfagpu_amd_align_device_linear_span with a span, or a metric configured with one, enters them), bit 7: the short-wavefront kernels
+ * of the one-component metrics (tier 5 under a metric: entered by an end-to-end metric call whose max_error / g is at most 30, or by
+ * wfagpu_amd_prime once a metric is configured).  Process-wide, never cleared.  A gap-affine end-to-end caller reads 0. */
 unsigned int wfagpu_amd_debug_code_objects(void);
 
 /* The HIP stream (hipStream_t) the context runs on -- its own, or the one given at creation. */

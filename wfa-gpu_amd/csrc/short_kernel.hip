@@ -18,6 +18,8 @@
 // wavefront_extend.c:47-67) and WFA2's CIGAR (see the note at the kernel).  Pairs whose window does not fit a group
 // (status BAND), whose score exceeds the budget (status SCORE) or that find the arena full (status NOMEM) go on to the
 // ordinary tiers / the next pass on the device like the failures of any tier.
+#include <algorithm>
+
 #include "short_kernel_impl.h"
 
 namespace {
@@ -32,9 +34,10 @@ const WfaShortEntry& short_pick(const WfaAlignParams& p, int lanes, bool with_bt
 }
 }  // namespace
 
-// arena units (16 bytes) a work item of a CIGAR launch owns: row table up to max_score + its rows
+// arena units (16 bytes) a work item of a CIGAR launch owns: row table up to max_score + its rows (a row of an 8-lane group -- the metric
+// kernels, short_kernel_lin.hip -- is padded to one unit)
 unsigned long long wfa_short_bt_slot_units(int max_score, int lanes) {
-  return (unsigned long long)(((long long)max_score + 2) >> 1) + (unsigned long long)(max_score + 1) * (unsigned)(lanes / 16);
+  return (unsigned long long)(((long long)max_score + 2) >> 1) + (unsigned long long)(max_score + 1) * (unsigned)(std::max(lanes, 16) / 16);
 }
 
 // (after the common-factor reduction: gap extensions to 4, history of eight scores)
@@ -43,7 +46,7 @@ bool wfa_short_supported(int x, int oe, int e) { return e >= 1 && e <= 4 && oe >
 // the staged sequences of the 64 / lanes pairs of a wavefront; with_bt: + their rows of origin bytes up to the launch's largest budget
 size_t wfa_short_lds_bytes(const WfaAlignParams& p, int lanes, bool with_bt) {
   const size_t seq = 2 * ((((size_t)(64 / lanes) * 2 * p.seq_words_cap) + 3) & ~(size_t)3) * 4;      // (two sets: this iteration's and the next one's)
-  return seq + (with_bt ? (size_t)64 * (size_t)(p.max_score + 1) : 0);
+  return seq + (with_bt ? (size_t)(64 / lanes) * (size_t)std::max(lanes, 16) * (size_t)(p.max_score + 1) : 0);
 }
 
 void wfa_launch_short(const WfaAlignParams& p, int lanes, bool with_bt, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {

@@ -317,8 +317,8 @@ void wfa_prime_trace_2p(hipStream_t stream);
 // (the backtrace of edit, indel and gap-linear alignments: trace_kernel_lin.hip, the same kernels compiled for one walk state and BTL_* origin bytes)
 bool wfa_launch_trace_lin(const WfaTraceParams& p, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 void wfa_prime_trace_lin(hipStream_t stream);
-// Tier 5 (short_kernel.hip): 64 / lanes alignments per wavefront (lanes = 16 or 32 diagonals each), rings in registers; with_bt: one row
-// of `lanes` origin bytes per score for the backtrace.
+// Tier 5 (short_kernel.hip): 64 / lanes alignments per wavefront (lanes = 16 or 32 diagonals each; 8 under a metric, below), rings in
+// registers; with_bt: one row of `lanes` origin bytes per score for the backtrace.
 bool wfa_short_supported(int x, int oe, int e);
 size_t wfa_short_lds_bytes(const WfaAlignParams& p, int lanes, bool with_bt);
 void wfa_launch_short(const WfaAlignParams& p, int lanes, bool with_bt, int grid, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
@@ -330,10 +330,17 @@ struct WfaShortEntry { void (*launch)(const WfaAlignParams&, int, hipStream_t, h
 const WfaShortEntry* wfa_short_entry_e2(int ascii, int bt, int l32, int idx);
 const WfaShortEntry* wfa_short_entry_e3(int ascii, int bt, int l32, int idx);
 const WfaShortEntry* wfa_short_entry_e4(int ascii, int bt, int l32, int idx);
+// Tier 5 under an edit, indel or gap-linear metric (short_kernel_lin.hip: a code object of its own, loaded only by metric calls whose
+// score budget fits it): lanes = 8, 16 or 32, the M ring in registers, BTL_* origin bytes.  x and g after the common-factor reduction
+// (x = WFA_LIN_NO_MISMATCH: indel).  wfa_short_lds_bytes and wfa_short_bt_slot_units serve it too (a row of 8 lanes is padded to 16 bytes).
+bool wfa_short_lin_supported(int x, int g);
+void wfa_launch_short_lin(const WfaAlignParams& p, int lanes, bool with_bt, int grid, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+int wfa_short_lin_max_blocks_per_cu(const WfaAlignParams& p, int lanes, bool with_bt);
+void wfa_prime_short_lin(hipStream_t stream);
 // Which of the optional code objects -- the ones only some callers load -- this process has entered: every host function that launches,
 // queries or primes a kernel of such a unit says so (the runtime loads a code object at the first of these).  Process-wide, never
 // cleared; wfagpu_amd_debug_code_objects() (wfa_host.hip) hands the bits out, tests check "never loaded" with them.
-enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u, WFA_UNIT_ALIGN_AD = 8u, WFA_UNIT_ALIGN_LIN = 16u, WFA_UNIT_TRACE_LIN = 32u, WFA_UNIT_ALIGN_LINEF = 64u };
+enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u, WFA_UNIT_ALIGN_AD = 8u, WFA_UNIT_ALIGN_LIN = 16u, WFA_UNIT_TRACE_LIN = 32u, WFA_UNIT_ALIGN_LINEF = 64u, WFA_UNIT_SHORT_LIN = 128u };
 void wfa_unit_entered(unsigned unit);
 // Code-object priming: one empty launch per kernel translation unit (see the definitions).
 void wfa_prime_pack(hipStream_t stream);

@@ -514,7 +514,8 @@ int wfagpu_amd_prime(wfagpu_amd_ctx_t* c) {
   if (wfa_configured_wfadaptive(nullptr)) wfa_prime_align_ad(c->stream);      // (the wf-adaptive kernels: only callers under the heuristic)
   // (the one-component kernels: only callers under such a metric -- the ends-free ones where it was configured with a span)
   if (wfa_configured_linear(nullptr)) {
-    if (wfa_configured_linear_span(nullptr)) wfa_prime_align_linef(c->stream); else wfa_prime_align_lin(c->stream);
+    // (tier 5 under a metric serves end-to-end calls only)
+    if (wfa_configured_linear_span(nullptr)) wfa_prime_align_linef(c->stream); else { wfa_prime_align_lin(c->stream); wfa_prime_short_lin(c->stream); }
     wfa_prime_trace_lin(c->stream);
   }
   LAUNCH_K(k_iota, dim3(1), dim3(64), 0, c->stream, static_cast<uint32_t*>(nullptr), 0u, 0u);      // (this file's)
@@ -639,6 +640,23 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
       const int nb = std::min(32, wfa_short_max_blocks_per_cu(p, lanes, bt));
       if (nb >= 1) {
         *out = {5, width, max_score, lds, nb, lanes};      // (wpe carries the lanes per alignment)
+        return true;
+      }
+    }
+  }
+  // The same under an edit, indel or gap-linear metric (short_kernel_lin.hip: M-only rings, 8, 16 or 32 lanes): width = S / g + 1 is the
+  // widest window of the budget; the smallest group with a lane to spare, as above -- 32 lanes up to S / g = 30, 16 up to 14, 8 up to 6.
+  // (No budgets are tuned under a metric: the tier is taken when the caller's max_error makes the window fit.)
+  if (lin && !ef && !raw && !(p.ascii && !c->short_ascii_ok) && c->tuning.min_tier == 0 && !(bt && c->tuning.no_short_cigar) && wfa_short_lin_supported(p.x, p.e) && width + 1 <= 32 && max_score <= 30000) {
+    // (tuning.waves_per_simd 16 / 32: at least that many lanes -- the A/B of the group widths, profiles/r14)
+    const int min_lanes = (c->tuning.waves_per_simd == 16 || c->tuning.waves_per_simd == 32) ? c->tuning.waves_per_simd : 8;
+    const int lanes = std::max(min_lanes, width + 1 <= 8 ? 8 : width + 1 <= 16 ? 16 : 32);
+    p.rs = 0;
+    const size_t lds = wfa_short_lds_bytes(p, lanes, bt);
+    if (lds <= 40u << 10) {
+      const int nb = std::min(32, wfa_short_lin_max_blocks_per_cu(p, lanes, bt));
+      if (nb >= 1) {
+        *out = {5, width, max_score, lds, nb, lanes};
         return true;
       }
     }
@@ -946,7 +964,9 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
   // 18 us + the gap between two launches of a 168 us step of 100k configs[1] pairs.  (ASCII dword indices are 32-bit there.)
   // (sequences_bytes may be missing from a caller's batch record: four times the packed words bound the ASCII layout from above)
   c->short_ascii_ok = std::max<size_t>(b->sequences_bytes, b->packed_bytes * 4) < ((size_t)1 << 34);
-  const bool short_fuses = !ef && !tp2 && !ad && !lin && wfa_short_supported(pen.x, oe, pen.e) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
+  // (a metric: the M-only kernels of short_kernel_lin.hip have the same ASCII variants; no budgets are tuned there, so the call's own
+  // max_error says whether the tier will be taken -- plan_tier's rule)
+  const bool short_fuses = !ef && !tp2 && !ad && (lin ? (wfa_short_lin_supported(ap.x, pen.e) && max_error / pen.e + 2 <= 32) : wfa_short_supported(pen.x, oe, pen.e)) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
   const bool fused_pack = !prepacked && (b->max_seq_len >= 512u || short_fuses) && !c->tuning.no_fused_pack;
   // Every status starts as PENDING = 0: written by the pack kernel where it runs (it visits every pair anyway), by a memset (a
   // launch of its own, ~5 us + a gap) where it does not -- queued by whoever reads the array first (ensure_status), and not at all
@@ -1195,7 +1215,8 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
         }
         // (L.e0 / L.e1: start and end of the wavefront kernel, stamped by its own dispatch packet)
         if (tp.tier == 5) {
-          wfa_launch_short(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
+          if (lin) wfa_launch_short_lin(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
+          else wfa_launch_short(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
           if (solo && !cigar_now) call_end = L.e1;      // (the chain's last kernel)
           // (with CIGARs the launch owns n_cur slots above the bump pointer: move it past them for whatever allocates next)
           if (cigar_now && !ap.arena_top_known) LAUNCH_K(k_bump, dim3(1), dim3(64), 0, st, ap.arena_top, (unsigned long long)n_cur * wfa_short_bt_slot_units(ap.max_score, tp.wpe), ap.arena_units);
