@@ -1,6 +1,9 @@
 // short_kernel_body.inc -- the body of the tier-5 kernels: wfa_short_kernel (short_kernel_impl.h, gap-affine: LIN == false) and
 // wfa_short_lin_kernel (short_kernel_lin.hip, the one-component metrics: LIN == true).  Textually included in both, where L, X, OE, E,
-// BT, ASCII, LIN and the kernel argument p are declared; the notes in front of wfa_short_kernel describe it.
+// BT, ASCII, LIN, EF and the kernel argument p are declared; the notes in front of wfa_short_kernel describe it.
+// EF (LIN only: wfa_short_linef_kernel, short_kernel_linef.hip): the metric under an ends-free span -- a start row, an interval of end
+// diagonals, the diagonal the alignment ended on to WfaAlignParams::ends.
+  static_assert(!EF || LIN, "a span: the one-component metrics only");
   static_assert(LIN ? (X >= 0 && X <= 8 && OE >= 1 && OE <= 4 && E == OE && (X > 0 || OE == 1)) : (X >= 1 && X <= 8 && OE >= 1 && OE <= 8 && E >= 1 && E <= OE && L >= 16), "history of eight scores");
   constexpr int D = X > OE ? X : OE;
   constexpr int RL = L < 16 ? 16 : L;     // bytes of a row of origin bytes: whole 16-byte units
@@ -168,6 +171,9 @@
     const int plen = active ? m0.plen : 0, tlen = active ? m0.tlen : 0;
     uint32_t* const Tw = Pw + cap;
     const int kend = tlen - plen;
+    // (EF) the span of this pair: each value clamped to its sequence's length (an inactive group: zeros)
+    int pbf = 0, pef = 0, tbf = 0, tef = 0;
+    if constexpr (EF) { pbf = min(p.span_pbf, plen); pef = min(p.span_pef, plen); tbf = min(p.span_tbf, tlen); tef = min(p.span_tef, tlen); }
     const int pwords = ((plen + 15) >> 4) + 1, twords = ((tlen + 15) >> 4) + 1;
     // the pair's score budget and the diagonal window that can hold an alignment within it (align_kernel.hip: a path that
     // visits diagonal k beyond both 0 and kend pays one gap out and one gap back)
@@ -180,7 +186,22 @@
     }
     uint32_t status = WFA_ST_DONE;
     int wlo = 0;
-    if constexpr (LIN) {
+    if constexpr (EF) {
+      // (align_kernel.hip, LINEAR && ENDSFREE: the hull of the start diagonals [-pbf, tbf] and the end diagonals [kend - tef, kend + pef],
+      // beyond it (gb - what the two intervals leave between them) / 2 -- quotients of non-negative numerators only)
+      if (active) {
+        const int s_lo = -pbf, s_hi = tbf, e_lo = kend - tef, e_hi = kend + pef;
+        const int hull_hi = max(s_hi, e_hi), hull_lo = min(s_lo, e_lo);
+        const long long gb = budget / OE;
+        const bool feasible = (long long)max(0, max(e_lo - s_hi, s_lo - e_hi)) <= gb;
+        const long long a_hi = gb + s_hi + e_hi, a_lo = gb - s_lo - e_lo;
+        int whi = a_hi >= 0 ? max(hull_hi, (int)min((long long)tlen, a_hi / 2)) : hull_hi;
+        wlo = a_lo >= 0 ? min(hull_lo, -(int)min((long long)plen, a_lo / 2)) : hull_lo;
+        whi = min(whi, tlen); wlo = max(wlo, -plen);
+        if (!feasible) status = WFA_ST_SCORE;
+        else if (whi - wlo + 1 > L || pwords > cap || twords > cap) status = WFA_ST_BAND;
+      }
+    } else if constexpr (LIN) {
       // (g (2 t + |kend|) <= S: t diagonals on either side of the end diagonals)
       if (active) {
         const int ak = kend < 0 ? -kend : kend, gb = budget / OE;
@@ -226,6 +247,11 @@
     const int h_hi = min(tlen, plen + k);
     const int h_lo = h_hi >= max(0, k) ? max(0, k) : INT_MAX / 2;      // (a diagonal that misses the matrix: nothing is inside)
     const uint32_t h_span = (uint32_t)max(h_hi - h_lo, 0);
+    // (EF) an end diagonal: a cell at the end of it -- h >= h_hi -- has used up the text with at most pef pattern bases left
+    // (kend <= k <= kend + pef, h_hi == tlen) or the pattern with at most tef text bases left (kend - tef <= k <= kend, h_hi == plen + k)
+    bool end_lane = false;
+    int end_k = 0;                                          // (EF) the diagonal the alignment ended on
+    if constexpr (EF) end_lane = k >= kend - tef && k <= kend + pef;
     __builtin_amdgcn_wave_barrier();                        // (one wavefront: LDS operations execute in order)
 
     // run length from (v, h) on this lane's diagonal, 16 bases per step, wave-uniform continuation
@@ -260,17 +286,24 @@
 #pragma unroll
     for (int i = 0; i < DG; ++i) { ig[i] = S_NULL; dg[i] = S_NULL; }
     {
-      const bool mine = run && k == 0;
-      const int h = extend(0, mine);
+      bool mine = run && k == 0;
+      int h_start = 0;
+      // (EF) the start row: every diagonal of [-pbf, tbf], from the border cell (wavefront_unialign.c:137-178)
+      if constexpr (EF) { mine = run && k >= -pbf && k <= tbf; h_start = max(k, 0); }
+      const int h = extend(h_start, mine);
       m[0] = mine ? h : S_NULL;
       if constexpr (BT) { if (run) lrows[0] = 0; }
     }
     bool fin = !run;                                        // this lane's group has its result (or never ran)
     int score = -1;
     {
-      const bool hit = run && k == kend && m[0] >= tlen;
+      bool hit = run && k == kend && m[0] >= tlen;
+      if constexpr (EF) hit = run && end_lane && m[0] >= h_hi;
       const unsigned long long bal = __builtin_amdgcn_ballot_w64(hit);
-      if (run && (bal & grp_mask) != 0ull) { fin = true; score = 0; }
+      if (run && (bal & grp_mask) != 0ull) {
+        fin = true; score = 0;
+        if constexpr (EF) end_k = (int)__builtin_ctzll(bal & grp_mask) - grp * L + wlo;
+      }
     }
     int s = 0;
     // one score: reads M[s - X], M[s - OE], I[s - E], D[s - E] from their registers (by value: one of them may be the register written)
@@ -319,10 +352,15 @@
       const bool ok = !fin & ((uint32_t)(mv - h_lo) <= h_span);
       const int h = extend(mv, ok);
       m_out = ok ? h : S_NULL;
-      const bool hit = ok && k == kend && h >= tlen;
+      bool hit = ok && k == kend && h >= tlen;
+      // (EF) the LOWEST diagonal of the group that ends the alignment wins (wavefront_extend.c:124-170)
+      if constexpr (EF) hit = ok && end_lane && h >= h_hi;
       const unsigned long long bal = __builtin_amdgcn_ballot_w64(hit);
       if (!fin) {
-        if ((bal & grp_mask) != 0ull) { fin = true; score = s; }
+        if ((bal & grp_mask) != 0ull) {
+          fin = true; score = s;
+          if constexpr (EF) end_k = (int)__builtin_ctzll(bal & grp_mask) - grp * L + wlo;
+        }
         else if (s >= budget) { fin = true; status = WFA_ST_SCORE; }
       }
     };
@@ -364,6 +402,8 @@
       const uint32_t cells = (status == WFA_ST_DONE) ? (uint32_t)(max(score, 0) + 1) * (uint32_t)L : 0u;
       if (p.cells) p.cells[pair] = cells;
       lane_rows += (status == WFA_ST_DONE) ? (uint32_t)(max(score, 0) + 1) : 0u;
+      // (EF) the diagonal the alignment ended on; the one it started on is the backtrace's to find
+      if constexpr (EF) { if (status == WFA_ST_DONE) { int32_t* const en = p.ends + 2 * (size_t)pair; en[0] = INT_MIN; en[1] = end_k; } }
     }
     {
       const bool failed = active && j == 0 && p.fail_list && (status == WFA_ST_BAND || status == WFA_ST_SCORE);

@@ -13,13 +13,16 @@ namespace {
 constexpr int S_NULL = -(1 << 28);
 
 // value of the lane one diagonal below (k - 1) / above (k + 1) within the group; lanes without such a neighbour get NULL
+// (L == 64: the whole wavefront is one group -- a DPP wave shift by one lane, NULL entering at lane 0 / lane 63)
 template <int L> __device__ __forceinline__ int from_below(int v, int j) {
-  if constexpr (L == 16) return __builtin_amdgcn_update_dpp(S_NULL, v, 0x111 /* row_shr:1 */, 0xF, 0xF, false);
+  if constexpr (L == 64) return __builtin_amdgcn_update_dpp(S_NULL, v, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
+  else if constexpr (L == 16) return __builtin_amdgcn_update_dpp(S_NULL, v, 0x111 /* row_shr:1 */, 0xF, 0xF, false);
   else if constexpr (L == 8) { const int r = __builtin_amdgcn_update_dpp(S_NULL, v, 0x111, 0xF, 0xF, false); return j == 0 ? S_NULL : r; }      // (a DPP row holds two groups)
   else { const int r = __shfl_up(v, 1, L); return j == 0 ? S_NULL : r; }
 }
 template <int L> __device__ __forceinline__ int from_above(int v, int j) {
-  if constexpr (L == 16) return __builtin_amdgcn_update_dpp(S_NULL, v, 0x101 /* row_shl:1 */, 0xF, 0xF, false);
+  if constexpr (L == 64) return __builtin_amdgcn_update_dpp(S_NULL, v, 0x130 /* wave_shl:1 */, 0xF, 0xF, false);
+  else if constexpr (L == 16) return __builtin_amdgcn_update_dpp(S_NULL, v, 0x101 /* row_shl:1 */, 0xF, 0xF, false);
   else if constexpr (L == 8) { const int r = __builtin_amdgcn_update_dpp(S_NULL, v, 0x101, 0xF, 0xF, false); return j == L - 1 ? S_NULL : r; }
   else { const int r = __shfl_down(v, 1, L); return j == L - 1 ? S_NULL : r; }
 }
@@ -63,7 +66,7 @@ template <int L> __device__ __forceinline__ int from_above(int v, int j) {
 template <int L, int X, int OE, int E, bool BT, bool ASCII>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((BT && E == 1) ? (ASCII ? 5 : 6) : 1, 8)))
 wfa_short_kernel(const WfaAlignParams p) {
-  constexpr bool LIN = false;
+  constexpr bool LIN = false, EF = false;
 #include "short_kernel_body.inc"
 }
 

@@ -18,7 +18,7 @@ namespace {
 template <int L, int X, int GAP, bool BT, bool ASCII>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8)))
 wfa_short_lin_kernel(const WfaAlignParams p) {
-  constexpr bool LIN = true;
+  constexpr bool LIN = true, EF = false;
   constexpr int OE = GAP, E = GAP;      // (every gap base costs g, nothing opens)
 #include "short_kernel_body.inc"
 }

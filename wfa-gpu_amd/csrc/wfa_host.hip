@@ -514,8 +514,7 @@ int wfagpu_amd_prime(wfagpu_amd_ctx_t* c) {
   if (wfa_configured_wfadaptive(nullptr)) wfa_prime_align_ad(c->stream);      // (the wf-adaptive kernels: only callers under the heuristic)
   // (the one-component kernels: only callers under such a metric -- the ends-free ones where it was configured with a span)
   if (wfa_configured_linear(nullptr)) {
-    // (tier 5 under a metric serves end-to-end calls only)
-    if (wfa_configured_linear_span(nullptr)) wfa_prime_align_linef(c->stream); else { wfa_prime_align_lin(c->stream); wfa_prime_short_lin(c->stream); }
+    if (wfa_configured_linear_span(nullptr)) { wfa_prime_align_linef(c->stream); wfa_prime_short_linef(c->stream); } else { wfa_prime_align_lin(c->stream); wfa_prime_short_lin(c->stream); }
     wfa_prime_trace_lin(c->stream);
   }
   LAUNCH_K(k_iota, dim3(1), dim3(64), 0, c->stream, static_cast<uint32_t*>(nullptr), 0u, 0u);      // (this file's)
@@ -655,6 +654,23 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     const size_t lds = wfa_short_lds_bytes(p, lanes, bt);
     if (lds <= 40u << 10) {
       const int nb = std::min(32, wfa_short_lin_max_blocks_per_cu(p, lanes, bt));
+      if (nb >= 1) {
+        *out = {5, width, max_score, lds, nb, lanes};
+        return true;
+      }
+    }
+  }
+  // A metric under a span (short_kernel_linef.hip: 16, 32 or 64 lanes): width is the bound from above -- S / g + 1 diagonals plus the
+  // clamped free bases --, which holds every pair's own window, hull or quotient: a pair the tier takes never comes back for a wider
+  // group.  The smallest group with a lane to spare; 64 lanes are one alignment per wavefront, still without an LDS ring.
+  if (lin && ef && !raw && !(p.ascii && !c->short_ascii_ok) && c->tuning.min_tier == 0 && !(bt && c->tuning.no_short_cigar) && wfa_short_lin_supported(p.x, p.e) && width + 1 <= 64 && max_score <= 30000) {
+    // (tuning.waves_per_simd 16 / 32 / 64: at least that many lanes -- the A/B of the group widths, profiles/r15)
+    const int min_lanes = (c->tuning.waves_per_simd == 16 || c->tuning.waves_per_simd == 32 || c->tuning.waves_per_simd == 64) ? c->tuning.waves_per_simd : 16;
+    const int lanes = std::max(min_lanes, width + 1 <= 16 ? 16 : width + 1 <= 32 ? 32 : 64);
+    p.rs = 0;
+    const size_t lds = wfa_short_lds_bytes(p, lanes, bt);
+    if (lds <= 40u << 10) {
+      const int nb = std::min(32, wfa_short_linef_max_blocks_per_cu(p, lanes, bt));
       if (nb >= 1) {
         *out = {5, width, max_score, lds, nb, lanes};
         return true;
@@ -966,7 +982,9 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
   c->short_ascii_ok = std::max<size_t>(b->sequences_bytes, b->packed_bytes * 4) < ((size_t)1 << 34);
   // (a metric: the M-only kernels of short_kernel_lin.hip have the same ASCII variants; no budgets are tuned there, so the call's own
   // max_error says whether the tier will be taken -- plan_tier's rule)
-  const bool short_fuses = !ef && !tp2 && !ad && (lin ? (wfa_short_lin_supported(ap.x, pen.e) && max_error / pen.e + 2 <= 32) : wfa_short_supported(pen.x, oe, pen.e)) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
+  // (under a span: plan_tier's bound -- S / g + 1 plus the clamped free bases -- within 64 lanes)
+  const long long ef_free = ef ? std::min<long long>(span->pattern_begin_free, batch_max_len) + std::min<long long>(span->pattern_end_free, batch_max_len) + std::min<long long>(span->text_begin_free, batch_max_len) + std::min<long long>(span->text_end_free, batch_max_len) : 0;
+  const bool short_fuses = !tp2 && !ad && (lin ? (wfa_short_lin_supported(ap.x, pen.e) && (ef ? std::min<long long>(2ll * batch_max_len + 1, max_error / pen.e + 1 + ef_free) + 1 <= 64 : max_error / pen.e + 2 <= 32)) : (!ef && wfa_short_supported(pen.x, oe, pen.e))) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
   const bool fused_pack = !prepacked && (b->max_seq_len >= 512u || short_fuses) && !c->tuning.no_fused_pack;
   // Every status starts as PENDING = 0: written by the pack kernel where it runs (it visits every pair anyway), by a memset (a
   // launch of its own, ~5 us + a gap) where it does not -- queued by whoever reads the array first (ensure_status), and not at all
@@ -1215,7 +1233,8 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
         }
         // (L.e0 / L.e1: start and end of the wavefront kernel, stamped by its own dispatch packet)
         if (tp.tier == 5) {
-          if (lin) wfa_launch_short_lin(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
+          if (lin && ef) wfa_launch_short_linef(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
+          else if (lin) wfa_launch_short_lin(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
           else wfa_launch_short(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
           if (solo && !cigar_now) call_end = L.e1;      // (the chain's last kernel)
           // (with CIGARs the launch owns n_cur slots above the bump pointer: move it past them for whatever allocates next)
