@@ -34,7 +34,7 @@ typedef struct {
     int waves_per_simd;    /* one-wave exact kernels: force the instantiation compiled for 8, 7, 6 or 4 waves per SIMD
                               (0: matched to the rings LDS lets a CU hold); tier 5 under a metric: 16 or 32 = at least that
                               many lanes per alignment (A/B of the 8- and 16-lane groups); tier 5 under a metric with a
-                              span: 16, 32 or 64 likewise                                                                  */
+                              span, or gap-affine under a span: 16, 32 or 64 likewise                                      */
     int trace_mode;        /* 0: automatic; 1: lane-per-alignment walk + windowed emit whatever the length (the fallback
                               of the wave-per-alignment kernel); 2: the wave-per-alignment kernel does the whole backtrace
                               (never several alignments per wavefront, never walk there + replay in the lane kernel); 3: never
@@ -178,7 +178,9 @@ void wfagpu_amd_debug_times(const wfagpu_amd_ctx_t* ctx, const void** d_records,
  * of the one-component metrics (tier 5 under a metric: entered by an end-to-end metric call whose max_error / g is at most 30, or by
  * wfagpu_amd_prime once a metric is configured), bit 8: the short-wavefront kernels of a metric under an ends-free span (entered by a
  * metric-with-span call whose window bound -- max_error / g + 1 plus the clamped free bases -- fits 64 lanes with one to spare, or by
- * wfagpu_amd_prime once a metric is configured with a span).  Process-wide, never cleared.  A gap-affine end-to-end caller reads 0. */
+ * wfagpu_amd_prime once a metric is configured with a span), bit 9: the short-wavefront kernels of gap-affine alignment under an
+ * ends-free span (entered by a gap-affine span call whose penalties the tier takes and whose window bound -- (max_error - o) / e + 1
+ * plus the clamped free bases -- fits 64 lanes with one to spare, or by wfagpu_amd_prime once a span is configured).  Process-wide, never cleared.  A gap-affine end-to-end caller reads 0. */
 unsigned int wfagpu_amd_debug_code_objects(void);
 
 /* The HIP stream (hipStream_t) the context runs on -- its own, or the one given at creation. */

@@ -1,9 +1,8 @@
 // short_kernel_body.inc -- the body of the tier-5 kernels: wfa_short_kernel (short_kernel_impl.h, gap-affine: LIN == false) and
 // wfa_short_lin_kernel (short_kernel_lin.hip, the one-component metrics: LIN == true).  Textually included in both, where L, X, OE, E,
 // BT, ASCII, LIN, EF and the kernel argument p are declared; the notes in front of wfa_short_kernel describe it.
-// EF (LIN only: wfa_short_linef_kernel, short_kernel_linef.hip): the metric under an ends-free span -- a start row, an interval of end
-// diagonals, the diagonal the alignment ended on to WfaAlignParams::ends.
-  static_assert(!EF || LIN, "a span: the one-component metrics only");
+// EF (wfa_short_linef_kernel, short_kernel_linef.hip: the metrics; wfa_short_ef_kernel, short_kernel_ef_impl.h: gap-affine): under an
+// ends-free span -- a start row, an interval of end diagonals, the diagonal the alignment ended on to WfaAlignParams::ends.
   static_assert(LIN ? (X >= 0 && X <= 8 && OE >= 1 && OE <= 4 && E == OE && (X > 0 || OE == 1)) : (X >= 1 && X <= 8 && OE >= 1 && OE <= 8 && E >= 1 && E <= OE && L >= 16), "history of eight scores");
   constexpr int D = X > OE ? X : OE;
   constexpr int RL = L < 16 ? 16 : L;     // bytes of a row of origin bytes: whole 16-byte units
@@ -186,7 +185,7 @@
     }
     uint32_t status = WFA_ST_DONE;
     int wlo = 0;
-    if constexpr (EF) {
+    if constexpr (EF && LIN) {
       // (align_kernel.hip, LINEAR && ENDSFREE: the hull of the start diagonals [-pbf, tbf] and the end diagonals [kend - tef, kend + pef],
       // beyond it (gb - what the two intervals leave between them) / 2 -- quotients of non-negative numerators only)
       if (active) {
@@ -197,6 +196,24 @@
         const long long a_hi = gb + s_hi + e_hi, a_lo = gb - s_lo - e_lo;
         int whi = a_hi >= 0 ? max(hull_hi, (int)min((long long)tlen, a_hi / 2)) : hull_hi;
         wlo = a_lo >= 0 ? min(hull_lo, -(int)min((long long)plen, a_lo / 2)) : hull_lo;
+        whi = min(whi, tlen); wlo = max(wlo, -plen);
+        if (!feasible) status = WFA_ST_SCORE;
+        else if (whi - wlo + 1 > L || pwords > cap || twords > cap) status = WFA_ST_BAND;
+      }
+    } else if constexpr (EF) {
+      // (align_kernel.hip, ENDSFREE: a path that visits a diagonal k above both intervals holds k - a bases of insertion and k - b of
+      // deletion, a in [-pbf, tbf], b in [kend - tef, kend + pef], in at least one gap each: 2o + (2k - a - b) e <= S, widest at a = tbf,
+      // b = kend + pef; below both, symmetric; between the hulls' ends every diagonal stays -- quotients of non-negative numerators only.
+      // feasible: the gap between the two intervals is affordable.  A span of zeros: the end-to-end formulas below.)
+      if (active) {
+        const int s_lo = -pbf, s_hi = tbf, e_lo = kend - tef, e_hi = kend + pef;
+        const int hull_hi = max(s_hi, e_hi), hull_lo = min(s_lo, e_lo);
+        const long long S = budget, o = OE - E;
+        const int gap = max(0, max(e_lo - s_hi, s_lo - e_hi));
+        const bool feasible = (gap ? o + (long long)gap * E : 0) <= S;
+        const long long a_hi = S - 2 * o + ((long long)s_hi + e_hi) * E, a_lo = S - 2 * o - ((long long)s_lo + e_lo) * E;
+        int whi = a_hi >= 0 ? max(hull_hi, (int)min((long long)tlen, a_hi / (2 * E))) : hull_hi;
+        wlo = a_lo >= 0 ? min(hull_lo, -(int)min((long long)plen, a_lo / (2 * E))) : hull_lo;
         whi = min(whi, tlen); wlo = max(wlo, -plen);
         if (!feasible) status = WFA_ST_SCORE;
         else if (whi - wlo + 1 > L || pwords > cap || twords > cap) status = WFA_ST_BAND;
@@ -331,10 +348,22 @@
       const bool ok = !fin & ((uint32_t)(mv - h_lo) <= h_span);
       const int h = extend(mv, ok);
       m_out = ok ? h : S_NULL;
-      const bool hit = ok && k == kend && h >= tlen;
+      bool hit = ok && k == kend && h >= tlen;
+      // (EF) an M cell at the end of an end diagonal; the LOWEST such diagonal of the group wins, as in step_lin.  I and D values never
+      // end an alignment: WFA2 scans the M wavefront (wavefront_extend.c:124-170), and a gap that reaches an end is in M at the same score.
+      // The note in front of wfa_short_kernel under a span -- an I (D) value nulled at once because it ran past the end of diagonal k came
+      // from a cell at the very end of the text (pattern) on diagonal k - 1 (k + 1) at a lower score, where M is at least as far.  If that
+      // neighbour is an end diagonal, the alignment ended there before this score.  If it is not, it lies beyond the interval of end
+      // diagonals and so does k: every path from cell (s, k) to ANY end diagonal crosses the neighbour behind an M offset that had
+      // reached its end at a lower score, and is dominated.  So the cells where nulling at once and WFA2's trimming differ are on no
+      // optimal path to any end diagonal, not only on none to the corner: scores, tie-breaks, end diagonal and CIGAR are WFA2's.
+      if constexpr (EF) hit = ok && end_lane && h >= h_hi;
       const unsigned long long bal = __builtin_amdgcn_ballot_w64(hit);
       if (!fin) {
-        if ((bal & grp_mask) != 0ull) { fin = true; score = s; }
+        if ((bal & grp_mask) != 0ull) {
+          fin = true; score = s;
+          if constexpr (EF) end_k = (int)__builtin_ctzll(bal & grp_mask) - grp * L + wlo;
+        }
         else if (s >= budget) { fin = true; status = WFA_ST_SCORE; }     // (the next score would be past the budget)
       }
     };

@@ -343,10 +343,21 @@ void wfa_prime_short_lin(hipStream_t stream);
 void wfa_launch_short_linef(const WfaAlignParams& p, int lanes, bool with_bt, int grid, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 int wfa_short_linef_max_blocks_per_cu(const WfaAlignParams& p, int lanes, bool with_bt);
 void wfa_prime_short_linef(hipStream_t stream);
+// Tier 5 for gap-affine alignment under an ends-free span (short_kernel_ef.hip and short_kernel_ef_e2/3/4.hip, one unit per gap extension
+// like the end-to-end ones: code objects of their own, loaded only by gap-affine span calls whose window bound fits a group): lanes = 16,
+// 32 or 64 -- 64: the wavefront is one alignment, its M, I and D rings still in registers --, BT_* origin bytes, the end diagonal to
+// WfaAlignParams::ends.  The penalties wfa_short_supported takes; wfa_short_lds_bytes and wfa_short_bt_slot_units serve it too.
+void wfa_launch_short_ef(const WfaAlignParams& p, int lanes, bool with_bt, int grid, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+int wfa_short_ef_max_blocks_per_cu(const WfaAlignParams& p, int lanes, bool with_bt);
+void wfa_prime_short_ef(hipStream_t stream);
+// (li: 0, 1, 2 for 16, 32, 64 lanes)
+const WfaShortEntry* wfa_short_ef_entry_e2(int ascii, int bt, int li, int idx);
+const WfaShortEntry* wfa_short_ef_entry_e3(int ascii, int bt, int li, int idx);
+const WfaShortEntry* wfa_short_ef_entry_e4(int ascii, int bt, int li, int idx);
 // Which of the optional code objects -- the ones only some callers load -- this process has entered: every host function that launches,
 // queries or primes a kernel of such a unit says so (the runtime loads a code object at the first of these).  Process-wide, never
 // cleared; wfagpu_amd_debug_code_objects() (wfa_host.hip) hands the bits out, tests check "never loaded" with them.
-enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u, WFA_UNIT_ALIGN_AD = 8u, WFA_UNIT_ALIGN_LIN = 16u, WFA_UNIT_TRACE_LIN = 32u, WFA_UNIT_ALIGN_LINEF = 64u, WFA_UNIT_SHORT_LIN = 128u, WFA_UNIT_SHORT_LINEF = 256u };
+enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u, WFA_UNIT_ALIGN_AD = 8u, WFA_UNIT_ALIGN_LIN = 16u, WFA_UNIT_TRACE_LIN = 32u, WFA_UNIT_ALIGN_LINEF = 64u, WFA_UNIT_SHORT_LIN = 128u, WFA_UNIT_SHORT_LINEF = 256u, WFA_UNIT_SHORT_EF = 512u };
 void wfa_unit_entered(unsigned unit);
 // Code-object priming: one empty launch per kernel translation unit (see the definitions).
 void wfa_prime_pack(hipStream_t stream);

@@ -509,7 +509,7 @@ int wfagpu_amd_prime(wfagpu_amd_ctx_t* c) {
   wfa_prime_trace(c->stream);
   wfa_prime_pack(c->stream);
   wfa_prime_short(c->stream);
-  if (wfa_configured_span(nullptr)) wfa_prime_align_ef(c->stream);      // (the ends-free kernels: only callers under a span load them)
+  if (wfa_configured_span(nullptr)) { wfa_prime_align_ef(c->stream); wfa_prime_short_ef(c->stream); }      // (the ends-free kernels: only callers under a span load them)
   if (wfa_configured_affine2p(nullptr)) { wfa_prime_align_2p(c->stream); wfa_prime_trace_2p(c->stream); }  // (the two-piece kernels: only callers under such penalties)
   if (wfa_configured_wfadaptive(nullptr)) wfa_prime_align_ad(c->stream);      // (the wf-adaptive kernels: only callers under the heuristic)
   // (the one-component kernels: only callers under such a metric -- the ends-free ones where it was configured with a span)
@@ -612,7 +612,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   }
   // Ends-free (p.ends): the window is the end-to-end one around the hull of the start and end diagonals -- wider by at most the
   // free bases (clamped to the sequences).  A bound for the longest pair, not an exact figure: a pair whose own window is wider
-  // comes back as a BAND failure and is escalated like any other.  Tiers 0, 1, 2 and 3 only.
+  // comes back as a BAND failure and is escalated like any other.  Tiers 0, 1, 2 and 3, and tier 5 where the bound fits a group (below).
   // Two pieces (p.e2 > 0): tiers 0, 1, 2 and 3 of the exact search, like ends-free; never combined with it.
   // wf-adaptive (p.ad_steps > 0): tiers 0, 1, 2 and 3 likewise, rings sized by window_width_ad; never combined with either.
   // One component (p.de == 0: edit, indel, gap-linear): tiers 0, 1, 2 and 3 likewise.  Its window -- (S / g - |kend|) / 2 diagonals on
@@ -671,6 +671,24 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     const size_t lds = wfa_short_lds_bytes(p, lanes, bt);
     if (lds <= 40u << 10) {
       const int nb = std::min(32, wfa_short_linef_max_blocks_per_cu(p, lanes, bt));
+      if (nb >= 1) {
+        *out = {5, width, max_score, lds, nb, lanes};
+        return true;
+      }
+    }
+  }
+  // Gap-affine under a span (short_kernel_ef.hip and its gap-extension units: 16, 32 or 64 lanes, M, I and D rings in registers): width
+  // is the bound from above -- (S - o) / e + 1 diagonals plus the clamped free bases, never more than every diagonal of the longest
+  // pair --, which holds every pair's own window, hull or quotient.  The smallest group with a lane to spare, as under the metric.
+  // (No budgets are tuned under a span: the tier is taken when the caller's max_error makes the bound fit.)
+  if (ef && !lin && !tp2 && !ad && !raw && !(p.ascii && !c->short_ascii_ok) && c->tuning.min_tier == 0 && !(bt && c->tuning.no_short_cigar) && wfa_short_supported(p.x, p.oe, p.e) && width + 1 <= 64 && max_score <= 30000) {
+    // (tuning.waves_per_simd 16 / 32 / 64: at least that many lanes -- the A/B of the group widths, profiles/r16)
+    const int min_lanes = (c->tuning.waves_per_simd == 16 || c->tuning.waves_per_simd == 32 || c->tuning.waves_per_simd == 64) ? c->tuning.waves_per_simd : 16;
+    const int lanes = std::max(min_lanes, width + 1 <= 16 ? 16 : width + 1 <= 32 ? 32 : 64);
+    p.rs = 0;
+    const size_t lds = wfa_short_lds_bytes(p, lanes, bt);
+    if (lds <= 40u << 10) {
+      const int nb = std::min(32, wfa_short_ef_max_blocks_per_cu(p, lanes, bt));
       if (nb >= 1) {
         *out = {5, width, max_score, lds, nb, lanes};
         return true;
@@ -982,9 +1000,9 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
   c->short_ascii_ok = std::max<size_t>(b->sequences_bytes, b->packed_bytes * 4) < ((size_t)1 << 34);
   // (a metric: the M-only kernels of short_kernel_lin.hip have the same ASCII variants; no budgets are tuned there, so the call's own
   // max_error says whether the tier will be taken -- plan_tier's rule)
-  // (under a span: plan_tier's bound -- S / g + 1 plus the clamped free bases -- within 64 lanes)
+  // (under a span: plan_tier's bound -- S / g + 1, gap-affine (S - o) / e + 1, plus the clamped free bases -- within 64 lanes)
   const long long ef_free = ef ? std::min<long long>(span->pattern_begin_free, batch_max_len) + std::min<long long>(span->pattern_end_free, batch_max_len) + std::min<long long>(span->text_begin_free, batch_max_len) + std::min<long long>(span->text_end_free, batch_max_len) : 0;
-  const bool short_fuses = !tp2 && !ad && (lin ? (wfa_short_lin_supported(ap.x, pen.e) && (ef ? std::min<long long>(2ll * batch_max_len + 1, max_error / pen.e + 1 + ef_free) + 1 <= 64 : max_error / pen.e + 2 <= 32)) : (!ef && wfa_short_supported(pen.x, oe, pen.e))) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
+  const bool short_fuses = !tp2 && !ad && (lin ? (wfa_short_lin_supported(ap.x, pen.e) && (ef ? std::min<long long>(2ll * batch_max_len + 1, max_error / pen.e + 1 + ef_free) + 1 <= 64 : max_error / pen.e + 2 <= 32)) : (wfa_short_supported(pen.x, oe, pen.e) && (!ef || std::min<long long>(2ll * batch_max_len + 1, window_width(max_error, pen.o, pen.e, batch_max_len) + ef_free) + 1 <= 64))) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
   const bool fused_pack = !prepacked && (b->max_seq_len >= 512u || short_fuses) && !c->tuning.no_fused_pack;
   // Every status starts as PENDING = 0: written by the pack kernel where it runs (it visits every pair anyway), by a memset (a
   // launch of its own, ~5 us + a gap) where it does not -- queued by whoever reads the array first (ensure_status), and not at all
@@ -1234,6 +1252,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
         // (L.e0 / L.e1: start and end of the wavefront kernel, stamped by its own dispatch packet)
         if (tp.tier == 5) {
           if (lin && ef) wfa_launch_short_linef(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
+          else if (ef) wfa_launch_short_ef(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
           else if (lin) wfa_launch_short_lin(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
           else wfa_launch_short(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
           if (solo && !cigar_now) call_end = L.e1;      // (the chain's last kernel)
