@@ -322,6 +322,25 @@ int wfagpu_amd_align_device_linear_span(wfagpu_amd_ctx_t* ctx, const wfagpu_amd_
  * three is configured, this call returns -1 and leaves the state alone.  A negative member or a bad metric: -1, state unchanged. */
 int wfagpu_amd_configure_linear_span(const wfagpu_amd_linear_t* linear, const wfagpu_amd_span_t* span);
 
+/* Two-piece penalties under an ends-free span: a long read placed in a window whose ends are fuzzy, extended from a seed, overlapped
+ * with another read or trimmed of an adapter, under the gap model long reads are aligned with.  wfagpu_amd_align_device_2p with the
+ * span and d_ends of wfagpu_amd_align_device_span (same meaning, same clamping, k0 = INT32_MIN in score-only calls), on kernels of
+ * their own; scores and CIGARs are WFA2's under gap_affine_2p with wavefront_aligner_set_alignment_free_ends, byte for byte: the free
+ * bases as D / I runs at the CIGAR's ends, merged with a gap of the same kind next to them, which is priced by the cheaper piece for
+ * its paid bases alone.  span == NULL: wfagpu_amd_align_device_2p (d_ends is not written); a span of zeros: the same results.
+ * A negative member of the span or a penalty <= 0: -1, before any device work.  Exact, tiers as for two pieces alone; not combined
+ * with a band, a metric or the heuristic. */
+int wfagpu_amd_align_device_2p_span(wfagpu_amd_ctx_t* ctx, const wfagpu_amd_batch_t* batch, const wfagpu_amd_penalties2p_t* penalties, int max_error,
+                                    const wfagpu_amd_span_t* span, bool compute_cigar, int32_t* d_scores, int32_t* d_ends,
+                                    const char** d_text, const unsigned long long** d_off, const unsigned int** d_len);
+
+/* Process-wide: the penalties of wfagpu_amd_configure_affine2p and their span, set together (span == NULL: end to end, which is what
+ * wfagpu_amd_configure_affine2p(penalties) means).  penalties == NULL clears both, as wfagpu_amd_configure_affine2p(NULL) does.
+ * While two-piece penalties are configured by either call, wfagpu_amd_configure_span, _linear and _wfadaptive return -1 as before;
+ * while a gap-affine span, a metric or the heuristic is configured, this call returns -1 and leaves the state alone.  A negative
+ * member or a penalty <= 0: -1, state unchanged. */
+int wfagpu_amd_configure_affine2p_span(const wfagpu_amd_penalties2p_t* penalties, const wfagpu_amd_span_t* span);
+
 void wfagpu_amd_last_stats(const wfagpu_amd_ctx_t* ctx, wfagpu_amd_stats_t* out);
 
 /* on = 1: the following calls on ctx align batches drawn from the same stream of reads (the batches of one

@@ -139,6 +139,7 @@ ABI_SYMBOLS = [
     "wfagpu_amd_align_device_adaptive", "wfagpu_amd_configure_wfadaptive",
     "wfagpu_amd_align_device_linear", "wfagpu_amd_configure_linear",
     "wfagpu_amd_align_device_linear_span", "wfagpu_amd_configure_linear_span",
+    "wfagpu_amd_align_device_2p_span", "wfagpu_amd_configure_affine2p_span",
 ]
 
 _lib = None
@@ -198,6 +199,11 @@ def load():
     lib.wfagpu_amd_align_device_linear_span.restype = C.c_int
     lib.wfagpu_amd_configure_linear_span.argtypes = [C.POINTER(Linear), C.POINTER(Span)]
     lib.wfagpu_amd_configure_linear_span.restype = C.c_int
+    lib.wfagpu_amd_align_device_2p_span.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Penalties2p), C.c_int, C.POINTER(Span), C.c_bool,
+                                                    C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.wfagpu_amd_align_device_2p_span.restype = C.c_int
+    lib.wfagpu_amd_configure_affine2p_span.argtypes = [C.POINTER(Penalties2p), C.POINTER(Span)]
+    lib.wfagpu_amd_configure_affine2p_span.restype = C.c_int
     lib.wfagpu_amd_debug_code_objects.argtypes = []
     lib.wfagpu_amd_debug_code_objects.restype = C.c_uint
     lib.wfagpu_amd_last_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
@@ -273,13 +279,17 @@ def configure_span(**kw):
         raise ValueError(f"wfagpu_amd_configure_span rejected {kw}")
 
 
-def configure_affine2p(pens=None):
+def configure_affine2p(pens=None, span=None):
     """wfagpu_amd_configure_affine2p: launch_alignments*, wfagpu_align and the CLI align under the two-piece penalties
     (x, o1, e1, o2, e2); the gap-affine penalties they are handed are ignored.  None: gap-affine again.  Raises ValueError when the
     library rejects them (a member <= 0, or a span is configured)."""
     lib = load()
     if pens is None:
         lib.wfagpu_amd_configure_affine2p(None)
+        return
+    if span is not None:      # (a Span, a dict of its fields or a 4-tuple; wfagpu_amd_configure_affine2p_span: the penalties run ends-free under it)
+        if lib.wfagpu_amd_configure_affine2p_span(C.byref(Penalties2p(*[int(v) for v in pens])), C.byref(_as_span(span))) != 0:
+            raise ValueError(f"wfagpu_amd_configure_affine2p_span rejected {tuple(pens)} under {span}")
         return
     if lib.wfagpu_amd_configure_affine2p(C.byref(Penalties2p(*[int(v) for v in pens]))) != 0:
         raise ValueError(f"wfagpu_amd_configure_affine2p rejected {tuple(pens)}")
@@ -579,8 +589,9 @@ class DeviceAligner:
         span: a Span, a dict of its fields or a 4-tuple (pattern begin, pattern end, text begin, text end free): ends-free alignment
         (wfagpu_amd_align_device_span; exact search, a band is an error).  fetch_ends (span only): a third result, int32[n, 2] =
         the start and end diagonals (k0, k1) of every pair (k0 is INT32_MIN in score-only calls).
-        affine2p: (x, o1, e1, o2, e2), two-piece gap-affine penalties (wfagpu_amd_align_device_2p; exact end-to-end search: a band or a
-        span is an error); `penalties` is ignored then.
+        affine2p: (x, o1, e1, o2, e2), two-piece gap-affine penalties (wfagpu_amd_align_device_2p; exact search: a band is an error);
+        `penalties` is ignored then.  With a span too: two pieces ends-free (wfagpu_amd_align_device_2p_span), fetch_ends as under a
+        span alone.
         wfadaptive: (min_wavefront_length, max_distance_threshold, steps_between_cutoffs), WFA2's wf-adaptive heuristic
         (wfagpu_amd_align_device_adaptive; end to end, gap-affine: a band, a span or two pieces is an error).
         linear: ("edit",), ("indel",) or ("linear", x, g), an edit, indel or gap-linear metric (wfagpu_amd_align_device_linear; exact
@@ -595,8 +606,8 @@ class DeviceAligner:
         t, o, l = C.c_void_p(), C.c_void_p(), C.c_void_p()
         pen = Penalties(*penalties) if (affine2p is None and linear is None) else Penalties(0, 0, 0)
         span = _as_span(span)
-        if affine2p is not None and (span is not None or (band > 0 and band_width > 0)):
-            raise ValueError("two-piece penalties are not combined with an ends-free span or the adaptive band")
+        if affine2p is not None and band > 0 and band_width > 0:
+            raise ValueError("two-piece penalties are not combined with the adaptive band")
         if wfadaptive is not None and (span is not None or affine2p is not None or (band > 0 and band_width > 0)):
             raise ValueError("the wf-adaptive heuristic is not combined with an ends-free span, two-piece penalties or the adaptive band")
         if linear is not None and (affine2p is not None or wfadaptive is not None or (band > 0 and band_width > 0)):
@@ -620,6 +631,10 @@ class DeviceAligner:
         elif wfadaptive is not None:
             rc = self.lib.wfagpu_amd_align_device_adaptive(self.ctx, C.byref(batch), pen, int(max_error), C.byref(WfAdaptive(*[int(v) for v in wfadaptive])),
                                                            bool(compute_cigar), d_scores.data_ptr(), C.byref(t), C.byref(o), C.byref(l))
+        elif affine2p is not None and span is not None:
+            rc = self.lib.wfagpu_amd_align_device_2p_span(self.ctx, C.byref(batch), C.byref(Penalties2p(*[int(v) for v in affine2p])), int(max_error), C.byref(span),
+                                                          bool(compute_cigar), d_scores.data_ptr(), d_ends.data_ptr() if d_ends is not None else None,
+                                                          C.byref(t), C.byref(o), C.byref(l))
         elif affine2p is not None:
             rc = self.lib.wfagpu_amd_align_device_2p(self.ctx, C.byref(batch), C.byref(Penalties2p(*[int(v) for v in affine2p])), int(max_error),
                                                      bool(compute_cigar), d_scores.data_ptr(), C.byref(t), C.byref(o), C.byref(l))

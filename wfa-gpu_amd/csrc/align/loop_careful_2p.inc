@@ -5,6 +5,9 @@
 // (:440-485), the wavefront is missing when all seven are (wavefront_compute_affine2p.c:340-350), end trimming for I1, D1, I2 and D2
 // (wavefront_compute.c:570-625), termination as for gap-affine (wavefront_extend.c:47-67).  The limits of I2 and D2 live in book2.
         ++s;
+        // (ENDSFREE: the reach interval surrounds an interval of end diagonals and outlives the budget by some scores: said here, the row
+        // table holds the scores up to the budget)
+        if constexpr (ENDSFREE) { if (s > budget) { status = WFA_ST_SCORE; break; } }
         // (past the budget the reach interval is empty, so that test sits on the "no wavefront" path; e_reach: align_kernel.hip)
         if (reach_r == 0) { ++rlo; --rhi; reach_r = e_reach - 1; } else --reach_r;
         if constexpr (NW > 1) {
@@ -102,20 +105,42 @@
         bool my_over = false;
         unsigned long long touch_mask = 0;
         cells_of_score(std::false_type{}, lo, hi, codes, p_x, p_oe - 1, p_ip - 1, d_of(p_ip) + 1, out_m, out_i, out_d, my_over, touch_mask);
+        // (ENDSFREE) termination (wavefront_extend.c:124-170, 240-262), as in loop_careful.inc: the LOWEST diagonal of the extended M row
+        // whose cell has used up the text with at most pef pattern bases left, or the pattern with at most tef text bases left.  Every
+        // wave scans the cells it has just written (the striping of cells_of_score, ascending: its first hit is its lowest); NW > 1: the
+        // minimum over the waves through word 0 of the score's reduction slot (the trimming below works on words 2..5), under the barrier
+        // the score has anyway.
+        int my_end = INT_MAX;
+        if constexpr (ENDSFREE) {
+          const int wave = (NW == 1) ? 0 : __builtin_amdgcn_readfirstlane(tid >> 6);
+          for (int k0 = lo; k0 <= hi; k0 += NT) {
+            const int kraw = k0 + tid;
+            const bool act = kraw <= hi;
+            const int k = act ? kraw : hi;
+            const int h = (int)out_m[k], v = h - k;
+            const bool hit = act && h >= 0 && ((h >= tlen && plen - v <= pef) || (v >= plen && tlen - h <= tef));
+            const unsigned long long bh = __builtin_amdgcn_ballot_w64(hit);
+            if (bh) { my_end = k0 + wave * 64 + (int)__builtin_ctzll(bh); break; }
+          }
+        }
         bool any_over = false;
         {
           const bool wave_over = __builtin_amdgcn_ballot_w64(my_over) != 0ull;
           if constexpr (NW == 1) {
             block_sync<NW>();
             any_over = wave_over;
+            if constexpr (ENDSFREE) end_k = my_end;
           } else {
             int* acc = red + 8 * (s % 3);
             if (lane == 0 && wave_over) atomicOr(&acc[6], 2);
+            if constexpr (ENDSFREE) { if (lane == 0 && my_end != INT_MAX) atomicMin(&acc[0], my_end); }
             __syncthreads();
             any_over = (acc[6] & 2) != 0;
+            if constexpr (ENDSFREE) end_k = acc[0];
           }
           // termination (wavefront_extend.c:47-67): every lane reads the same cell
-          done = ((unsigned)(kend - lo) <= (unsigned)(hi - lo)) && __builtin_amdgcn_readfirstlane((int)out_m[kend]) >= tlen;
+          if constexpr (ENDSFREE) done = end_k != INT_MAX;
+          else done = ((unsigned)(kend - lo) <= (unsigned)(hi - lo)) && __builtin_amdgcn_readfirstlane((int)out_m[kend]) >= tlen;
         }
         // Limits recorded for the row: the computed ones.  Cells that are not valid hold NULL or a negative value, which is all a
         // reader needs; only values past a sequence end need the exact per-component trimming: first / last in-range cell.

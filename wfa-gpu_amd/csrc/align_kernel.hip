@@ -216,13 +216,16 @@ __device__ __forceinline__ ColdParams cold_params() {
 // LINEAR && ENDSFREE (align_kernel_linef.hip includes this file for those instantiations): a one-component metric under a span -- the
 // start row and the epilogue of ENDSFREE on the M-only ring of LINEAR, the score step of LINEAR with the lowest-diagonal termination of
 // ENDSFREE, a window of its own (below).  DESIGN.md section 4.10.
+// TWOPIECE && ENDSFREE (align_kernel_2pef.hip includes this file for those instantiations): two pieces under a span -- the start row and
+// the epilogue of ENDSFREE on the five-component ring of TWOPIECE, the score step of TWOPIECE with the lowest-diagonal termination of
+// ENDSFREE, a window of its own (below: a concave gap cost between two intervals of diagonals).  DESIGN.md section 4.14.
 template <int NW, bool BT, typename OffT, bool GLOBAL_RING, bool RAW, bool BANDED, bool HYBRID = false, int WPE = 8, bool TIMED = false, bool ENDSFREE = false,
           bool TWOPIECE = false, bool ADAPTIVE = false, bool LINEAR = false>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu((NW == 1 && !BANDED) ? WPE : 1, 8)))
 wfa_align_kernel(const WfaAlignParams p) {
   static_assert(!HYBRID || (!GLOBAL_RING && !BANDED), "the hybrid ring is an exact LDS tier");
   static_assert(!ENDSFREE || (!BANDED && !HYBRID && !TIMED), "ends-free: the exact search of tiers 0, 1, 2 and 3");
-  static_assert(!TWOPIECE || (!BANDED && !HYBRID && !TIMED && !ENDSFREE), "two pieces: the end-to-end exact search of tiers 0, 1, 2 and 3");
+  static_assert(!TWOPIECE || (!BANDED && !HYBRID && !TIMED), "two pieces: the exact search of tiers 0, 1, 2 and 3, end to end or ends-free");
   static_assert(!ADAPTIVE || (!BANDED && !HYBRID && !TIMED && !ENDSFREE && !TWOPIECE), "wf-adaptive: end to end, gap-affine, tiers 0, 1, 2 and 3");
   static_assert(!LINEAR || (!BANDED && !HYBRID && !TIMED && !TWOPIECE && !ADAPTIVE), "one component: the exact search of tiers 0, 1, 2 and 3, end to end or ends-free");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -410,6 +413,24 @@ wfa_align_kernel(const WfaAlignParams p) {
         feasible = ak <= gb;
         const int t = feasible ? (gb - ak) / 2 : 0;
         whi = min(max(0, kend) + t, tlen); wlo = max(min(0, kend) - t, -plen);
+      }
+    } else if constexpr (TWOPIECE && ENDSFREE) {
+      // Two pieces under a span: a path starts on a diagonal a of S = [-pbf, tbf] and ends on a diagonal b of E = [kend - tef, kend + pef].
+      // One that visits a diagonal k above both intervals holds at least k - a inserted and k - b deleted bases, in one gap each or in
+      // more; g is increasing and subadditive (wfa_device.h), so it costs at least g(k - a) + g(k - b) >= g(k - tbf) + g(k - kend - pef).
+      // With H = max(tbf, kend + pef) and k = H + t the two distances are t + (H - tbf) and t + (H - kend - pef), one of them t itself:
+      // whi = H + the largest t >= 0 within the budget (wfa_stray2p_between: a bisection on the scalar unit, once per alignment), and H
+      // where not even t = 0 is -- between the hulls' ends every diagonal stays, a path may simply start or end there.  Below both,
+      // symmetric: g(-pbf - k) + g(kend - tef - k) against L = min(-pbf, kend - tef).  feasible: the gap between the two intervals is
+      // affordable.  With a span of zeros H = max(0, kend), L = min(0, kend), the distances are t and t + |kend| on either side and
+      // the gap is |kend|: the end-to-end formulas of the branch below.
+      const int s_lo = -pbf, s_hi = tbf, e_lo = kend - tef, e_hi = kend + pef;
+      const int H = max(s_hi, e_hi), L = min(s_lo, e_lo);
+      if (budget < INT_MAX / 2) {
+        feasible = wfa_gap2p(max(0, max(e_lo - s_hi, s_lo - e_hi)), oe, e, oe2, e2) <= (long long)budget;
+        const int t_hi = feasible ? wfa_stray2p_between(budget, H - s_hi, H - e_hi, oe, e, oe2, e2) : 0;
+        const int t_lo = feasible ? wfa_stray2p_between(budget, s_lo - L, e_lo - L, oe, e, oe2, e2) : 0;
+        whi = (int)min((long long)H + t_hi, (long long)tlen); wlo = (int)max((long long)L - t_lo, -(long long)plen);
       }
     } else if constexpr (TWOPIECE) {
       // Two pieces.  A gap of n bases costs g(n) = min(o1 + n e1, o2 + n e2), and g is subadditive (wfa_device.h), so a path that visits a
@@ -613,6 +634,7 @@ wfa_align_kernel(const WfaAlignParams p) {
         }
         ncells = (uint32_t)(pbf + tbf + 1);
         book.set(0, pack_range(-pbf, tbf), ROW_NONE_A, ROW_NONE_A);
+        if constexpr (TWOPIECE) book2.set(0, ROW_NONE_A, ROW_NONE_A);      // (no I1, D1, I2 or D2 at score 0)
         done = end_k != INT_MAX;
       }
       if (!ENDSFREE && tid == 0) {
@@ -799,7 +821,50 @@ int occ_inst(size_t lds) {
   return nb;
 }
 
-#if defined(WFA_ALIGN_LINEF_UNIT)
+#if defined(WFA_ALIGN_2PEF_UNIT)
+// ---- the translation unit of two-piece penalties under a span (align_kernel_2pef.hip): tiers 0, 1, 2 and 3, with and without
+// backtrace, packed and byte-compare
+template <bool BT, bool RAW>
+void launch_tier_2pef(const WfaAlignParams& p, int tier, size_t lds, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  switch (tier) {
+    case 0: launch_inst<1, BT, int16_t, false, RAW, false, false, 8, false, true, true>(p, lds, grid, stream, ev0, ev1); break;
+    case 1: launch_inst<4, BT, int16_t, false, RAW, false, false, 8, false, true, true>(p, lds, grid, stream, ev0, ev1); break;
+    case 2: launch_inst<16, BT, int16_t, false, RAW, false, false, 8, false, true, true>(p, lds, grid, stream, ev0, ev1); break;
+    default:
+      if (p.ring16) launch_inst<16, BT, int16_t, true, RAW, false, false, 8, false, true, true>(p, lds, grid, stream, ev0, ev1);
+      else launch_inst<16, BT, int32_t, true, RAW, false, false, 8, false, true, true>(p, lds, grid, stream, ev0, ev1);
+      break;
+  }
+}
+template <bool BT, bool RAW>
+int occ_tier_2pef(int tier, size_t lds) {
+  switch (tier) {
+    case 0: return occ_inst<1, BT, int16_t, false, RAW, false, false, 8, true, true>(lds);
+    case 1: return occ_inst<4, BT, int16_t, false, RAW, false, false, 8, true, true>(lds);
+    case 2: return occ_inst<16, BT, int16_t, false, RAW, false, false, 8, true, true>(lds);
+    default: return occ_inst<16, BT, int32_t, true, RAW, false, false, 8, true, true>(lds);
+  }
+}
+
+}  // namespace
+
+void wfa_launch_align_2pef(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  wfa_unit_entered(WFA_UNIT_ALIGN_2PEF);
+  const size_t lds = wfa_align_lds_bytes(p, tier);
+  if (with_bt) { if (raw) launch_tier_2pef<true, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_2pef<true, false>(p, tier, lds, grid, stream, ev0, ev1); }
+  else { if (raw) launch_tier_2pef<false, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_2pef<false, false>(p, tier, lds, grid, stream, ev0, ev1); }
+}
+
+int wfa_align_2pef_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds) {
+  wfa_unit_entered(WFA_UNIT_ALIGN_2PEF);
+  if (with_bt) return raw ? occ_tier_2pef<true, true>(tier, lds) : occ_tier_2pef<true, false>(tier, lds);
+  return raw ? occ_tier_2pef<false, true>(tier, lds) : occ_tier_2pef<false, false>(tier, lds);
+}
+
+// (this code object is loaded by the first launch of one of its kernels: wfagpu_amd_prime does that only under two-piece penalties configured with a span)
+namespace { __global__ void k_prime_align_2pef() {} }
+void wfa_prime_align_2pef(hipStream_t stream) { wfa_unit_entered(WFA_UNIT_ALIGN_2PEF); hipLaunchKernelGGL(k_prime_align_2pef, dim3(1), dim3(64), 0, stream); }
+#elif defined(WFA_ALIGN_LINEF_UNIT)
 // ---- the translation unit of the one-component metrics under a span (align_kernel_linef.hip): tiers 0, 1, 2 and 3, with and without
 // backtrace, packed and byte-compare
 template <bool BT, bool RAW>

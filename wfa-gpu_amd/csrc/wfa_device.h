@@ -87,6 +87,18 @@ __host__ __device__ inline int wfa_stray2p(const long long S, const long long ak
   return (int)lo;
 }
 
+// The same between two intervals of diagonals (two pieces under a span): the largest t >= 0 with g(t + da) + g(t + db) <= S, da, db >= 0
+// -- a path that strays t diagonals beyond the hull of its start and end diagonals holds t + da bases of one kind and t + db of the
+// other.  0 where not even t = 0 is within S.  wfa_stray2p(S, ak) is the case (0, ak).
+__host__ __device__ inline int wfa_stray2p_between(const long long S, const long long da, const long long db, const int oe1, const int e1, const int oe2, const int e2) {
+  long long lo = 0, hi = wfa_reach2p(S / 2, oe1, e1, oe2, e2);      // (2 g(t) <= S bounds it)
+  while (lo < hi) {
+    const long long mid = lo + (hi - lo + 1) / 2;
+    if (wfa_gap2p(mid + da, oe1, e1, oe2, e2) + wfa_gap2p(mid + db, oe1, e1, oe2, e2) <= S) lo = mid; else hi = mid - 1;
+  }
+  return (int)lo;
+}
+
 // Operations of a reversed op list (what the backward walk leaves for the replay): the kind, and whether a run of matches
 // follows the operation (re-derived by the replay as a longest common prefix).
 enum : uint8_t { OP_X = 1, OP_I = 2, OP_D = 3, OP_EXT_AFTER = 0x10 };
@@ -305,6 +317,18 @@ void wfa_launch_align_linef(const WfaAlignParams& p, int tier, bool with_bt, boo
                             hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 int wfa_align_linef_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds_bytes);
 void wfa_prime_align_linef(hipStream_t stream);
+// The instantiations for two-piece penalties under an ends-free span (align_kernel_2pef.hip: a code object of their own, loaded only by
+// such calls): tiers 0, 1, 2 and 3, exact search, careful loop, origin bytes in ROWS; the two-piece backtrace kernels serve them as they
+// are (the span travels in WfaTraceParams).  wfa_align_lds_bytes serves them too (WfaAlignParams::e2 > 0).
+void wfa_launch_align_2pef(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream,
+                           hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+int wfa_align_2pef_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds_bytes);
+void wfa_prime_align_2pef(hipStream_t stream);
+// The span that wfagpu_amd_configure_affine2p_span set with its penalties (wfa_launch.hip): false when the configured penalties run end
+// to end, or none are configured; out (optional) receives the four members.  wfa_lane_affine2p_span4: the span the calling thread -- a
+// lane of launch_alignments* -- wants its two-piece penalties to run under (nullptr: end to end).
+bool wfa_configured_affine2p_span(int* out4);
+const int* wfa_lane_affine2p_span4();
 // The span that wfagpu_amd_configure_linear_span set with its metric (wfa_launch.hip): false when the configured metric runs end to
 // end, or none is configured; out (optional) receives the four members.  wfa_lane_linear_span4: the span the calling thread -- a lane
 // of launch_alignments* -- wants its metric to run under (nullptr: end to end).
@@ -357,7 +381,7 @@ const WfaShortEntry* wfa_short_ef_entry_e4(int ascii, int bt, int li, int idx);
 // Which of the optional code objects -- the ones only some callers load -- this process has entered: every host function that launches,
 // queries or primes a kernel of such a unit says so (the runtime loads a code object at the first of these).  Process-wide, never
 // cleared; wfagpu_amd_debug_code_objects() (wfa_host.hip) hands the bits out, tests check "never loaded" with them.
-enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u, WFA_UNIT_ALIGN_AD = 8u, WFA_UNIT_ALIGN_LIN = 16u, WFA_UNIT_TRACE_LIN = 32u, WFA_UNIT_ALIGN_LINEF = 64u, WFA_UNIT_SHORT_LIN = 128u, WFA_UNIT_SHORT_LINEF = 256u, WFA_UNIT_SHORT_EF = 512u };
+enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u, WFA_UNIT_ALIGN_AD = 8u, WFA_UNIT_ALIGN_LIN = 16u, WFA_UNIT_TRACE_LIN = 32u, WFA_UNIT_ALIGN_LINEF = 64u, WFA_UNIT_SHORT_LIN = 128u, WFA_UNIT_SHORT_LINEF = 256u, WFA_UNIT_SHORT_EF = 512u, WFA_UNIT_ALIGN_2PEF = 1024u };
 void wfa_unit_entered(unsigned unit);
 // Code-object priming: one empty launch per kernel translation unit (see the definitions).
 void wfa_prime_pack(hipStream_t stream);

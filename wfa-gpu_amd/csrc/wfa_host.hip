@@ -510,7 +510,8 @@ int wfagpu_amd_prime(wfagpu_amd_ctx_t* c) {
   wfa_prime_pack(c->stream);
   wfa_prime_short(c->stream);
   if (wfa_configured_span(nullptr)) { wfa_prime_align_ef(c->stream); wfa_prime_short_ef(c->stream); }      // (the ends-free kernels: only callers under a span load them)
-  if (wfa_configured_affine2p(nullptr)) { wfa_prime_align_2p(c->stream); wfa_prime_trace_2p(c->stream); }  // (the two-piece kernels: only callers under such penalties)
+  // (the two-piece kernels: only callers under such penalties -- the ends-free ones where they were configured with a span)
+  if (wfa_configured_affine2p(nullptr)) { if (wfa_configured_affine2p_span(nullptr)) wfa_prime_align_2pef(c->stream); else wfa_prime_align_2p(c->stream); wfa_prime_trace_2p(c->stream); }
   if (wfa_configured_wfadaptive(nullptr)) wfa_prime_align_ad(c->stream);      // (the wf-adaptive kernels: only callers under the heuristic)
   // (the one-component kernels: only callers under such a metric -- the ends-free ones where it was configured with a span)
   if (wfa_configured_linear(nullptr)) {
@@ -613,7 +614,10 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   // Ends-free (p.ends): the window is the end-to-end one around the hull of the start and end diagonals -- wider by at most the
   // free bases (clamped to the sequences).  A bound for the longest pair, not an exact figure: a pair whose own window is wider
   // comes back as a BAND failure and is escalated like any other.  Tiers 0, 1, 2 and 3, and tier 5 where the bound fits a group (below).
-  // Two pieces (p.e2 > 0): tiers 0, 1, 2 and 3 of the exact search, like ends-free; never combined with it.
+  // Two pieces (p.e2 > 0): tiers 0, 1, 2 and 3 of the exact search, like ends-free.
+  // Two pieces under a span (p.e2 > 0 and p.ends: align_kernel_2pef.hip): rings with the two-piece row counts, window_width_2p widened by
+  // the free bases like the gap-affine span -- the kernel's window is the stray of the budget on either side of the hull of the start
+  // and end diagonals, and the hull is at most the free bases wider than [min(0, kend), max(0, kend)].
   // wf-adaptive (p.ad_steps > 0): tiers 0, 1, 2 and 3 likewise, rings sized by window_width_ad; never combined with either.
   // One component (p.de == 0: edit, indel, gap-linear): tiers 0, 1, 2 and 3 likewise.  Its window -- (S / g - |kend|) / 2 diagonals on
   // either side of the end diagonals -- is widest at |kend| = S / g: S / g + 1 diagonals, which is window_width with o = 0; its ring is
@@ -709,7 +713,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     if (t == 0 && (width > 1024 || p.dm > 64)) continue;
     if (t == 1 && width > 8192) continue;
     if (t == 1 && few_pairs && width >= 1024 && !min_tier && wfa_align_lds_bytes(p, 2) <= budget[2]) continue;
-    int nb = (lin && ef) ? wfa_align_linef_max_blocks_per_cu(t, bt, raw, lds) : lin ? wfa_align_lin_max_blocks_per_cu(t, bt, raw, lds) : ad ? wfa_align_ad_max_blocks_per_cu(t, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(t, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(t, bt, raw, lds) : wfa_align_max_blocks_per_cu(t, bt, raw, false, lds);
+    int nb = (lin && ef) ? wfa_align_linef_max_blocks_per_cu(t, bt, raw, lds) : (tp2 && ef) ? wfa_align_2pef_max_blocks_per_cu(t, bt, raw, lds) : lin ? wfa_align_lin_max_blocks_per_cu(t, bt, raw, lds) : ad ? wfa_align_ad_max_blocks_per_cu(t, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(t, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(t, bt, raw, lds) : wfa_align_max_blocks_per_cu(t, bt, raw, false, lds);
     if (nb < 1) continue;
     // Occupancy-matched instantiation of the one-wave kernels: LDS decides how many rings a CU holds; compiled for 8 waves
     // per SIMD the kernel lives on 64 VGPRs and 78 SGPRs (123 scalar spills + scratch), which only pays when 8 waves per
@@ -753,7 +757,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   p.rs = rs_plain;
   const size_t lds = wfa_align_lds_bytes(p, 3);
   if (lds > c->lds_per_block_max) return false;   // sequences themselves do not fit LDS
-  const int nb = (lin && ef) ? wfa_align_linef_max_blocks_per_cu(3, bt, raw, lds) : lin ? wfa_align_lin_max_blocks_per_cu(3, bt, raw, lds) : ad ? wfa_align_ad_max_blocks_per_cu(3, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(3, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(3, bt, raw, lds) : wfa_align_max_blocks_per_cu(3, bt, raw, false, lds);
+  const int nb = (lin && ef) ? wfa_align_linef_max_blocks_per_cu(3, bt, raw, lds) : (tp2 && ef) ? wfa_align_2pef_max_blocks_per_cu(3, bt, raw, lds) : lin ? wfa_align_lin_max_blocks_per_cu(3, bt, raw, lds) : ad ? wfa_align_ad_max_blocks_per_cu(3, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(3, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(3, bt, raw, lds) : wfa_align_max_blocks_per_cu(3, bt, raw, false, lds);
   *out = {3, width, max_score, lds, std::max(1, std::min(nb, 2))};
   return true;
 }
@@ -779,7 +783,8 @@ int zero_counter(wfagpu_amd_ctx* c, int idx, int count = 1) {
 }  // namespace
 
 // span == nullptr: end to end.  Else the ends-free kernels (align_kernel_ef.hip), exact search; d_ends: see the header.
-// pen2 != nullptr: two-piece gap-affine (align_kernel_2p.hip), exact search, end to end; `pen` is ignored.
+// pen2 != nullptr: two-piece gap-affine (align_kernel_2p.hip), exact search, end to end; `pen` is ignored.  With a span: ends-free
+// (align_kernel_2pef.hip: the two are combined through wfagpu_amd_align_device_2p_span alone).
 static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
                              affine_penalties_t pen, int max_error, int band, int band_width,
                              bool compute_cigar, int32_t* d_scores,
@@ -817,7 +822,6 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
     return -1;
   }
   if (ef || tp2 || ad) { band = -1; band_width = 0; }      // (exact search: a band is a permission to approximate, not an obligation; wf-adaptive: its own heuristic)
-  if (tp2 && ef) { fprintf(stderr, "[!] ERROR: two-piece penalties are not combined with an ends-free span\n"); return -1; }
   int o2 = 0, e2 = 0;      // the second piece (pen holds x and the first)
   if (tp2) {
     // (WFA2 rejects anything else: wavefront_penalties_set_affine2p)
@@ -960,7 +964,8 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
     est_pair_bytes = 0.5 * (B + 1) * (B + 1) / std::min(pen.e, e2) + 16.0 * B + 4096.0;
   }
   if (ef) {
-    // (ends-free: every score's row starts as wide as the free begins and only grows: rows behind a row table in every tier)
+    // (ends-free: every score's row starts as wide as the free begins and only grows: rows behind a row table in every tier; two pieces
+    // under a span: the two-piece diamond from above plus this)
     const double m = batch_max_len;
     const double start_w = std::min<double>(span->pattern_begin_free, m) + std::min<double>(span->text_begin_free, m) + 1.0;
     est_pair_bytes += start_w * (double)std::min<unsigned>(max_error, 2 * max_len);
@@ -1260,6 +1265,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
           if (cigar_now && !ap.arena_top_known) LAUNCH_K(k_bump, dim3(1), dim3(64), 0, st, ap.arena_top, (unsigned long long)n_cur * wfa_short_bt_slot_units(ap.max_score, tp.wpe), ap.arena_units);
         }
         else if (lin && ef) wfa_launch_align_linef(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
+        else if (tp2 && ef) wfa_launch_align_2pef(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else if (ef) wfa_launch_align_ef(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else if (tp2) wfa_launch_align_2p(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else if (ad) wfa_launch_align_ad(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
@@ -1730,6 +1736,12 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
   const int* const l2 = wfa_lane_affine2p5();
   if (l2) {
     const wfagpu_amd_penalties2p_t p2{l2[0], l2[1], l2[2], l2[3], l2[4]};
+    // (configured with a span -- wfagpu_amd_configure_affine2p_span --: the lane hands that over too)
+    const int* const l2s = wfa_lane_affine2p_span4();
+    if (l2s) {
+      const wfagpu_amd_span_t span{l2s[0], l2s[1], l2s[2], l2s[3]};
+      return align_device_impl(c, b, pen, max_error, band, band_width, compute_cigar, d_scores, d_text, d_off, d_len, &span, nullptr, &p2);
+    }
     return align_device_impl(c, b, pen, max_error, band, band_width, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, &p2);
   }
   // (and for a configured edit, indel or gap-linear metric: wfagpu_amd_configure_linear -- the penalties handed in are ignored)
@@ -1781,6 +1793,15 @@ extern "C" int wfagpu_amd_align_device_2p(wfagpu_amd_ctx_t* c, const wfagpu_amd_
                                           const unsigned int** d_len) {
   if (!pens) { fprintf(stderr, "[!] ERROR: wfagpu_amd_align_device_2p needs penalties\n"); return -1; }
   return align_device_impl(c, b, affine_penalties_t{}, max_error, -1, 0, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, pens);
+}
+
+extern "C" int wfagpu_amd_align_device_2p_span(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b, const wfagpu_amd_penalties2p_t* pens, int max_error,
+                                               const wfagpu_amd_span_t* span, bool compute_cigar, int32_t* d_scores, int32_t* d_ends,
+                                               const char** d_text, const unsigned long long** d_off, const unsigned int** d_len) {
+  if (!pens) { fprintf(stderr, "[!] ERROR: wfagpu_amd_align_device_2p_span needs penalties\n"); return -1; }
+  // (NULL: the end-to-end kernels, d_ends is left alone.  A span of zeros runs the ends-free kernels -- a start row of one cell, one
+  // end diagonal, the end-to-end window -- and gives the same bytes.)
+  return align_device_impl(c, b, affine_penalties_t{}, max_error, -1, 0, compute_cigar, d_scores, d_text, d_off, d_len, span, span ? d_ends : nullptr, pens);
 }
 
 extern "C" int wfagpu_amd_align_device_span(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b, affine_penalties_t pen, int max_error,

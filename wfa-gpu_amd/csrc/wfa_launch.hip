@@ -56,6 +56,11 @@ thread_local const int* t_lane_span = nullptr;
 bool g_2p_set = false;
 int g_2p[5] = {0, 0, 0, 0, 0};
 thread_local const int* t_lane_2p = nullptr;
+// The span two-piece penalties were configured with (wfagpu_amd_configure_affine2p_span): part of the penalties' state -- set and
+// cleared with them, never g_span, which stays the gap-affine span's -- and handed over the same way (wfa_lane_affine2p_span4).
+bool g_2p_span_set = false;
+int g_2p_span[4] = {0, 0, 0, 0};
+thread_local const int* t_lane_2p_span = nullptr;
 // The process-wide wf-adaptive heuristic (wfagpu_amd_configure_wfadaptive), the same way (wfa_lane_wfadaptive3); under the same
 // mutex: never configured together with a span or two-piece penalties.
 bool g_ad_set = false;
@@ -156,11 +161,24 @@ bool wfa_configured_affine2p(int* out5) {
   return g_2p_set;
 }
 const int* wfa_lane_affine2p5() { return t_lane_2p; }
+bool wfa_configured_affine2p_span(int* out4) {
+  std::lock_guard<std::mutex> lock(g_span_mutex);
+  const bool set = g_2p_set && g_2p_span_set;
+  if (out4 && set) for (int i = 0; i < 4; ++i) out4[i] = g_2p_span[i];
+  return set;
+}
+const int* wfa_lane_affine2p_span4() { return t_lane_2p_span; }
 
-extern "C" int wfagpu_amd_configure_affine2p(const wfagpu_amd_penalties2p_t* pens) {
+// (one body for wfagpu_amd_configure_affine2p -- sp == nullptr: these penalties end to end -- and wfagpu_amd_configure_affine2p_span)
+static int configure_affine2p_impl(const wfagpu_amd_penalties2p_t* pens, const wfagpu_amd_span_t* sp) {
   if (pens && (pens->mismatch <= 0 || pens->gap_opening1 <= 0 || pens->gap_extension1 <= 0 || pens->gap_opening2 <= 0 || pens->gap_extension2 <= 0)) {
     fprintf(stderr, "[!] ERROR: two-piece penalties must all be positive (got %d,%d,%d,%d,%d)\n", pens->mismatch, pens->gap_opening1, pens->gap_extension1,
             pens->gap_opening2, pens->gap_extension2);
+    return -1;
+  }
+  if (pens && sp && (sp->pattern_begin_free < 0 || sp->pattern_end_free < 0 || sp->text_begin_free < 0 || sp->text_end_free < 0)) {
+    fprintf(stderr, "[!] ERROR: the members of a span must not be negative (got %d,%d,%d,%d)\n", sp->pattern_begin_free, sp->pattern_end_free,
+            sp->text_begin_free, sp->text_end_free);
     return -1;
   }
   std::lock_guard<std::mutex> lock(g_span_mutex);
@@ -178,8 +196,14 @@ extern "C" int wfagpu_amd_configure_affine2p(const wfagpu_amd_penalties2p_t* pen
   }
   g_2p_set = pens != nullptr;
   if (pens) { g_2p[0] = pens->mismatch; g_2p[1] = pens->gap_opening1; g_2p[2] = pens->gap_extension1; g_2p[3] = pens->gap_opening2; g_2p[4] = pens->gap_extension2; }
+  // (the penalties' span goes with them: NULL penalties or NULL span -- end to end)
+  g_2p_span_set = pens != nullptr && sp != nullptr;
+  if (g_2p_span_set) { g_2p_span[0] = sp->pattern_begin_free; g_2p_span[1] = sp->pattern_end_free; g_2p_span[2] = sp->text_begin_free; g_2p_span[3] = sp->text_end_free; }
   return 0;
 }
+
+extern "C" int wfagpu_amd_configure_affine2p(const wfagpu_amd_penalties2p_t* pens) { return configure_affine2p_impl(pens, nullptr); }
+extern "C" int wfagpu_amd_configure_affine2p_span(const wfagpu_amd_penalties2p_t* pens, const wfagpu_amd_span_t* span) { return configure_affine2p_impl(pens, span); }
 
 extern "C" int wfagpu_amd_configure_span(const wfagpu_amd_span_t* span) {
   if (span && (span->pattern_begin_free < 0 || span->pattern_end_free < 0 || span->text_begin_free < 0 || span->text_end_free < 0)) {
@@ -335,6 +359,10 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
   // (under configured two-piece penalties: a gap run priced by the cheaper piece, the score checked against the five-table program)
   int q5[5] = {0, 0, 0, 0, 0};
   const int* const p2 = wfa_configured_affine2p(q5) ? q5 : nullptr;
+  // (two-piece penalties configured with a span: the text priced without its free runs, each paid run by the cheaper piece, the score
+  // checked against the five-table program with free borders)
+  int ps4[4] = {0, 0, 0, 0};
+  const int* const p2span = (p2 && wfa_configured_affine2p_span(ps4)) ? ps4 : nullptr;
   // (under a configured wf-adaptive heuristic: the CIGAR is valid and costs the score as always; the score may lie ABOVE the CPU
   // scorer's optimum -- such pairs are counted and said, they are no failures; a score below the optimum is one)
   const bool heuristic = wfa_configured_wfadaptive(nullptr);
@@ -365,6 +393,7 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
           const bool c1 = check_cigar_edit(text, pattern, m.text_len, m.pattern_len, cg);
           const bool c2 = lspan ? check_linear_distance_span(text, pattern, m.text_len, m.pattern_len, dist, lm[0], lm[1], lm[2], cg, lspan)
                         : lm ? check_linear_distance(text, pattern, m.text_len, m.pattern_len, dist, lm[0], lm[1], lm[2], cg)
+                        : p2span ? check_affine2p_distance_span(text, pattern, m.text_len, m.pattern_len, dist, p2[0], p2[1], p2[2], p2[3], p2[4], cg, p2span)
                         : p2 ? check_affine2p_distance(text, pattern, m.text_len, m.pattern_len, dist, p2[0], p2[1], p2[2], p2[3], p2[4], cg)
                         : span ? check_affine_distance_span(text, pattern, m.text_len, m.pattern_len, dist, a.opt.penalties.x,
                                                             a.opt.penalties.o, a.opt.penalties.e, cg, span)
@@ -375,6 +404,7 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
         }
         const int cpu = lspan ? verification_cpu_score_linear_span(pattern, text, m.pattern_len, m.text_len, lm[0], lm[1], lm[2], lspan)
                       : lm ? verification_cpu_score_linear(pattern, text, m.pattern_len, m.text_len, lm[0], lm[1], lm[2])
+                      : p2span ? verification_cpu_score_2p_span(pattern, text, m.pattern_len, m.text_len, p2[0], p2[1], p2[2], p2[3], p2[4], p2span)
                       : p2 ? verification_cpu_score_2p_scratch(pattern, text, m.pattern_len, m.text_len, p2[0], p2[1], p2[2], p2[3], p2[4], &scratch)
                       : span ? verification_cpu_score_span_scratch(pattern, text, m.pattern_len, m.text_len, a.opt.penalties.x,
                                                                    a.opt.penalties.o, a.opt.penalties.e, span, &scratch)
@@ -1086,6 +1116,8 @@ int run_device(const CallArgs& a, Shard& sh) {
         }
       }
       t_lane_2p = under_2p ? q5 : nullptr;
+      int q4[4];
+      t_lane_2p_span = (under_2p && wfa_configured_affine2p_span(q4)) ? q4 : nullptr;
       // (and for a configured wf-adaptive heuristic -- wfagpu_amd_configure_wfadaptive --: a band is not used, said once)
       int h3[3];
       const bool under_ad = wfa_configured_wfadaptive(h3);
@@ -1110,6 +1142,7 @@ int run_device(const CallArgs& a, Shard& sh) {
                                               d_sc, &bo.d_text, &bo.d_off, &bo.d_len);
       t_lane_span = nullptr;
       t_lane_2p = nullptr;
+      t_lane_2p_span = nullptr;
       t_lane_ad = nullptr;
       t_lane_lin = nullptr;
       t_lane_lin_span = nullptr;

@@ -70,6 +70,8 @@ static void usage(const char* prog) {
            "\t                                  (each of the three: not with another, -g, -B, --ends-free, --affine2p or --wfa-adaptive)\n"
            "\t    --metric-ends-free <pb,pe,tb,te> --edit, --indel or --gap-linear under an ends-free span (the members as for --ends-free):\n"
            "\t                                  only together with one of the three; not with -B, --ends-free, --affine2p or --wfa-adaptive\n"
+           "\t    --affine2p-ends-free <pb,pe,tb,te> --affine2p under an ends-free span (the members as for --ends-free): only together with\n"
+           "\t                                  --affine2p; not with -g, -B, --ends-free, --metric-ends-free, a metric or --wfa-adaptive\n"
            "[System]\n"
            "\t-t, --threads-per-block <int>     Accepted for compatibility (band width in banded mode)\n"
            "\t-w, --workers <int>               Accepted for compatibility\n"
@@ -94,7 +96,8 @@ int main(int argc, char** argv) {
         {"workers", required_argument, 0, 'w'}, {"help", no_argument, 0, 'h'}, {"stage-times", no_argument, 0, 1000},
         {"ends-free", required_argument, 0, 1001}, {"affine2p", required_argument, 0, 1002},
         {"wfa-adaptive", required_argument, 0, 1003}, {"edit", no_argument, 0, 1004}, {"indel", no_argument, 0, 1005},
-        {"gap-linear", required_argument, 0, 1006}, {"metric-ends-free", required_argument, 0, 1007}, {0, 0, 0, 0}};
+        {"gap-linear", required_argument, 0, 1006}, {"metric-ends-free", required_argument, 0, 1007},
+        {"affine2p-ends-free", required_argument, 0, 1008}, {0, 0, 0, 0}};
     const char *seq_path = NULL, *q_path = NULL, *t_path = NULL, *out_path = NULL, *pen_str = NULL;
     long n_read = 0, max_distance = -1, batch_size = -1, band_arg = -2, tpb = -1, workers = -1;
     bool print_out = false, verbose = false, cigar = false, check = false, stage_times = false;
@@ -103,6 +106,7 @@ int main(int argc, char** argv) {
     const char* wfad_str = NULL;
     const char* lin_str = NULL;
     const char* mspan_str = NULL;
+    const char* p2span_str = NULL;
     int n_metric = 0, metric = -1;
 
 
@@ -133,6 +137,7 @@ int main(int argc, char** argv) {
             case 1005: metric = WFAGPU_AMD_METRIC_INDEL; ++n_metric; break;
             case 1006: metric = WFAGPU_AMD_METRIC_GAP_LINEAR; lin_str = optarg; ++n_metric; break;
             case 1007: mspan_str = optarg; break;      /* (not in the reference: a metric under WFA2's ends-free alignment) */
+            case 1008: p2span_str = optarg; break;     /* (not in the reference: gap_affine_2p under WFA2's ends-free alignment) */
             case 'h': usage(argv[0]); exit(0);
             default: break;      /* an option the tool does not know is skipped, like the reference's parser does (utils/arg_handler.c:97-140) */
         }
@@ -143,6 +148,27 @@ int main(int argc, char** argv) {
         return 1;
     }
 
+    /* --affine2p-ends-free: four non-negative integers, nothing behind them; only together with --affine2p, not together with -g, -B,
+     * --ends-free, --metric-ends-free, a metric or --wfa-adaptive.  Checked first of all, before any device work and before
+     * another option could configure anything; the block of --affine2p below configures the two together. */
+    int p2span4[4] = {0, 0, 0, 0};
+    if (p2span_str) {
+        if (!span_arg_parse(p2span_str, p2span4)) {
+            LOG_ERROR("--affine2p-ends-free takes four non-negative integers pb,pe,tb,te (got \"%s\").", p2span_str)
+            usage(argv[0]);
+            return 1;
+        }
+        if (!pen2_str) {
+            LOG_ERROR("--affine2p-ends-free is the span of two-piece penalties: it goes together with --affine2p.")
+            usage(argv[0]);
+            return 1;
+        }
+        if (pen_str || band_arg != -2 || span_str || mspan_str || n_metric || wfad_str) {
+            LOG_ERROR("--affine2p-ends-free is an exact search under two-piece penalties: it is not combined with -g, -B, --ends-free, --metric-ends-free, a metric or --wfa-adaptive.")
+            usage(argv[0]);
+            return 1;
+        }
+    }
     /* --metric-ends-free: four non-negative integers, nothing behind them; only together with exactly one of --edit, --indel and
      * --gap-linear, not together with -B, --ends-free, --affine2p or --wfa-adaptive.  Checked first of all, and like the others before
      * any device work; the metric's own block below configures the two together. */
@@ -200,6 +226,11 @@ int main(int argc, char** argv) {
             usage(argv[0]);
             return 1;
         }
+        if (p2span_str) {
+            const wfagpu_amd_span_t p2span = {p2span4[0], p2span4[1], p2span4[2], p2span4[3]};
+            if (wfagpu_amd_configure_affine2p_span(&pen2, &p2span) != 0) return 1;
+            LOG_INFO("Ends-free under two-piece penalties: pattern begin/end free %d/%d, text begin/end free %d/%d.", p2span4[0], p2span4[1], p2span4[2], p2span4[3])
+        } else
         if (wfagpu_amd_configure_affine2p(&pen2) != 0) return 1;
         LOG_INFO("Two-piece gap-affine penalties: M=0, X=%d, O1=%d, E1=%d, O2=%d, E2=%d.", pen2.mismatch, pen2.gap_opening1, pen2.gap_extension1,
                  pen2.gap_opening2, pen2.gap_extension2)

@@ -371,6 +371,106 @@ int verification_cpu_score_2p_scratch(const char* pattern, const char* text, siz
     return s;
 }
 
+/* ---- two-piece gap-affine under an ends-free span (see verification.h) ---- */
+bool check_affine2p_distance_span(const char* text, const char* pattern, size_t tlen, size_t plen,
+                                  int distance, int x, int o1, int e1, int o2, int e2, const char* cigar, const int* span) {
+    (void)text; (void)pattern;
+    int pb, pe, tb, te;
+    clamp_span(span, (int)plen, (int)tlen, &pb, &pe, &tb, &te);
+    /* items first: the last one is only known at the end */
+    size_t n_items = 0;
+    for (const char* c = cigar; *c;) { long n; char op; c = next_item(c, &n, &op); if (!c) return false; ++n_items; }
+    long cost = 0;
+    size_t idx = 0;
+    const char* c = cigar;
+    while (*c) {
+        long n = 0; char op = 0;
+        c = next_item(c, &n, &op);      /* (well-formed: checked above; run-length encoded: an item is a whole run) */
+        if (op == 'I' || op == 'D') {
+            long paid = n;
+            if (idx == 0) { const long f = op == 'I' ? tb : pb; paid -= f < paid ? f : paid; }
+            if (idx + 1 == n_items) { const long f = op == 'I' ? te : pe; paid -= f < paid ? f : paid; }
+            if (paid > 0) cost += gap2p_cost(paid, o1, e1, o2, e2);
+        } else if (op == 'X') cost += n * x;
+        else if (op != 'M') return false;
+        ++idx;
+    }
+    return cost == distance;
+}
+
+/* The program of verification_cpu_score_2p_scratch with the free borders of verification_cpu_score_span_scratch. */
+int verification_cpu_score_2p_span(const char* pattern, const char* text, size_t plen_, size_t tlen_,
+                                   int x, int o1, int e1, int o2, int e2, const int* span) {
+    const int plen = (int)plen_, tlen = (int)tlen_;
+    int pbf, pef, tbf, tef;
+    clamp_span(span, plen, tlen, &pbf, &pef, &tbf, &tef);
+    const int W = plen + tlen + 5, K0 = plen + 2;
+    const int NONE = -(1 << 28);
+    const int oe[2] = {o1 + e1, o2 + e2}, ex[2] = {e1, e2};
+    int depth = x;
+    if (oe[0] > depth) depth = oe[0];
+    if (oe[1] > depth) depth = oe[1];
+    ++depth;
+    int* const buf = (int*)malloc(sizeof(int) * (size_t)W * 5 * (size_t)depth);
+    if (!buf) return -1;
+    int* T[5];      /* M, I1, D1, I2, D2 */
+    for (int t = 0; t < 5; ++t) T[t] = buf + (size_t)t * W * depth;
+    int lo = -pbf, hi = tbf, s = 0;
+    bool ended = false;
+    for (int t = 0; t < 5; ++t)
+        for (int r = 0; r < depth; ++r)
+            for (int k = lo - 1; k <= hi + 1; ++k) T[t][(size_t)r * W + K0 + k] = NONE;
+    for (int k = lo; k <= hi; ++k) {
+        int h = k > 0 ? k : 0, v = h - k;
+        while (v < plen && h < tlen && pattern[v] == text[h]) { ++v; ++h; }
+        T[0][K0 + k] = h;
+        if ((h >= tlen && plen - v <= pef) || (v >= plen && tlen - h <= tef)) ended = true;
+    }
+    while (!ended) {
+        ++s;
+        const size_t row = (size_t)(s % depth) * W;
+        const int* Mx = s >= x ? T[0] + (size_t)((s - x) % depth) * W : NULL;
+        if (lo > -plen) {
+            --lo;
+            for (int t = 0; t < 5; ++t) for (int r = 0; r < depth; ++r) T[t][(size_t)r * W + K0 + lo - 1] = NONE;
+        }
+        if (hi < tlen) {
+            ++hi;
+            for (int t = 0; t < 5; ++t) for (int r = 0; r < depth; ++r) T[t][(size_t)r * W + K0 + hi + 1] = NONE;
+        }
+        for (int k = lo; k <= hi; ++k) {
+            int m = NONE;
+            if (Mx && Mx[K0 + k] >= 0) m = Mx[K0 + k] + 1;
+            if (m >= 0 && (m > tlen || m - k > plen)) m = NONE;
+            for (int pc = 0; pc < 2; ++pc) {
+                const int* Mo = s >= oe[pc] ? T[0] + (size_t)((s - oe[pc]) % depth) * W : NULL;
+                const int* Ie = s >= ex[pc] ? T[1 + 2 * pc] + (size_t)((s - ex[pc]) % depth) * W : NULL;
+                const int* De = s >= ex[pc] ? T[2 + 2 * pc] + (size_t)((s - ex[pc]) % depth) * W : NULL;
+                int ins = NONE, del = NONE;
+                if (Mo && Mo[K0 + k - 1] > ins) ins = Mo[K0 + k - 1];
+                if (Ie && Ie[K0 + k - 1] > ins) ins = Ie[K0 + k - 1];
+                if (ins >= 0) ++ins;
+                if (Mo && Mo[K0 + k + 1] > del) del = Mo[K0 + k + 1];
+                if (De && De[K0 + k + 1] > del) del = De[K0 + k + 1];
+                if (ins >= 0 && (ins > tlen || ins - k > plen)) ins = NONE;
+                if (del >= 0 && (del > tlen || del - k > plen)) del = NONE;
+                T[1 + 2 * pc][row + K0 + k] = ins; T[2 + 2 * pc][row + K0 + k] = del;
+                if (ins > m) m = ins;
+                if (del > m) m = del;
+            }
+            if (m >= 0) {
+                int h = m, v = m - k;
+                while (v < plen && h < tlen && pattern[v] == text[h]) { ++v; ++h; }
+                m = h;
+                if ((h >= tlen && plen - v <= pef) || (v >= plen && tlen - h <= tef)) ended = true;
+            }
+            T[0][row + K0 + k] = m;
+        }
+    }
+    free(buf);
+    return s;
+}
+
 int verification_heuristic_verdict(int distance, int optimum) {
     if (distance < optimum) return -1;
     return distance - optimum;

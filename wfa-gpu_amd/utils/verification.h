@@ -79,6 +79,15 @@ bool check_linear_distance_span(const char* text, const char* pattern, size_t tl
                                 int distance, int metric, int x, int g, const char* cigar, const int* span);
 int verification_cpu_score_linear_span(const char* pattern, const char* text, size_t plen, size_t tlen, int metric, int x, int g, const int* span);
 
+/* Two-piece penalties under an ends-free span (wfagpu_amd_align_device_2p_span, --affine2p-ends-free): span as above.  The CIGAR is
+ * priced WITHOUT its free bases -- a leading D (I) run is free for as many bases as pattern_begin_free (text_begin_free) allows, a
+ * trailing one for pattern_end_free (text_end_free) --, each run by the cheaper piece for its paid bases; the score checked against
+ * the five-table scalar program with free borders. */
+bool check_affine2p_distance_span(const char* text, const char* pattern, size_t tlen, size_t plen,
+                                  int distance, int x, int o1, int e1, int o2, int e2, const char* cigar, const int* span);
+int verification_cpu_score_2p_span(const char* pattern, const char* text, size_t plen, size_t tlen,
+                                   int x, int o1, int e1, int o2, int e2, const int* span);
+
 #ifdef __cplusplus
 }
 #endif
