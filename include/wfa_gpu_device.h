@@ -341,6 +341,21 @@ int wfagpu_amd_align_device_2p_span(wfagpu_amd_ctx_t* ctx, const wfagpu_amd_batc
  * member or a penalty <= 0: -1, state unchanged. */
 int wfagpu_amd_configure_affine2p_span(const wfagpu_amd_penalties2p_t* penalties, const wfagpu_amd_span_t* span);
 
+/* The wf-adaptive heuristic under two-piece penalties: WFA2's defaults for long reads, both at once (gap_affine_2p 4,6,2,24,1 with
+ * wavefront_aligner_set_heuristic_wfadaptive; the cut-off equates I1, D1, I2 and D2 to M's limits).  wfagpu_amd_align_device_2p plus
+ * the heuristic of wfagpu_amd_align_device_adaptive, on kernels of their own; scores and CIGARs are WFA2's under the same parameters,
+ * byte for byte; the score can lie above the two-piece optimum.  heuristic == NULL: wfagpu_amd_align_device_2p.  A penalty <= 0 or a
+ * bad heuristic member (as above): -1.  End to end (no band, no span). */
+int wfagpu_amd_align_device_2p_adaptive(wfagpu_amd_ctx_t* ctx, const wfagpu_amd_batch_t* batch, const wfagpu_amd_penalties2p_t* penalties, int max_error,
+                                        const wfagpu_amd_wfadaptive_t* heuristic, bool compute_cigar, int32_t* d_scores,
+                                        const char** d_text, const unsigned long long** d_off, const unsigned int** d_len);
+
+/* Process-wide, like wfagpu_amd_configure_span: launch_alignments*, wfagpu_align and the CLI align under these two pieces and this
+ * heuristic; the affine_penalties_t they are handed is ignored, a band that is asked for is not used (said once on stderr).  Either
+ * argument NULL: cleared, gap-affine and exact again.  A bad member, or a span, plain two-piece penalties, the plain heuristic or a
+ * metric are configured: rejected (-1, message), state unchanged -- as are those four while this pair is configured. */
+int wfagpu_amd_configure_affine2p_wfadaptive(const wfagpu_amd_penalties2p_t* penalties, const wfagpu_amd_wfadaptive_t* heuristic);
+
 void wfagpu_amd_last_stats(const wfagpu_amd_ctx_t* ctx, wfagpu_amd_stats_t* out);
 
 /* on = 1: the following calls on ctx align batches drawn from the same stream of reads (the batches of one

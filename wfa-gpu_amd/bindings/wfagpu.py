@@ -140,6 +140,7 @@ ABI_SYMBOLS = [
     "wfagpu_amd_align_device_linear", "wfagpu_amd_configure_linear",
     "wfagpu_amd_align_device_linear_span", "wfagpu_amd_configure_linear_span",
     "wfagpu_amd_align_device_2p_span", "wfagpu_amd_configure_affine2p_span",
+    "wfagpu_amd_align_device_2p_adaptive", "wfagpu_amd_configure_affine2p_wfadaptive",
 ]
 
 _lib = None
@@ -204,6 +205,11 @@ def load():
     lib.wfagpu_amd_align_device_2p_span.restype = C.c_int
     lib.wfagpu_amd_configure_affine2p_span.argtypes = [C.POINTER(Penalties2p), C.POINTER(Span)]
     lib.wfagpu_amd_configure_affine2p_span.restype = C.c_int
+    lib.wfagpu_amd_align_device_2p_adaptive.argtypes = [C.c_void_p, C.POINTER(Batch), C.POINTER(Penalties2p), C.c_int, C.POINTER(WfAdaptive), C.c_bool,
+                                                        C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.wfagpu_amd_align_device_2p_adaptive.restype = C.c_int
+    lib.wfagpu_amd_configure_affine2p_wfadaptive.argtypes = [C.POINTER(Penalties2p), C.POINTER(WfAdaptive)]
+    lib.wfagpu_amd_configure_affine2p_wfadaptive.restype = C.c_int
     lib.wfagpu_amd_debug_code_objects.argtypes = []
     lib.wfagpu_amd_debug_code_objects.restype = C.c_uint
     lib.wfagpu_amd_last_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
@@ -279,13 +285,22 @@ def configure_span(**kw):
         raise ValueError(f"wfagpu_amd_configure_span rejected {kw}")
 
 
-def configure_affine2p(pens=None, span=None):
+def configure_affine2p(pens=None, span=None, wfadaptive=None):
     """wfagpu_amd_configure_affine2p: launch_alignments*, wfagpu_align and the CLI align under the two-piece penalties
     (x, o1, e1, o2, e2); the gap-affine penalties they are handed are ignored.  None: gap-affine again.  Raises ValueError when the
-    library rejects them (a member <= 0, or a span is configured)."""
+    library rejects them (a member <= 0, or a span is configured).
+    wfadaptive: (min_wavefront_length, max_distance_threshold, steps_between_cutoffs) -- the penalties run under WFA2's wf-adaptive
+    heuristic (wfagpu_amd_configure_affine2p_wfadaptive; not with a span).  None penalties clear that pair too."""
     lib = load()
     if pens is None:
         lib.wfagpu_amd_configure_affine2p(None)
+        lib.wfagpu_amd_configure_affine2p_wfadaptive(None, None)
+        return
+    if wfadaptive is not None:
+        if span is not None:
+            raise ValueError("two-piece penalties under the wf-adaptive heuristic are not combined with an ends-free span")
+        if lib.wfagpu_amd_configure_affine2p_wfadaptive(C.byref(Penalties2p(*[int(v) for v in pens])), C.byref(WfAdaptive(*[int(v) for v in wfadaptive]))) != 0:
+            raise ValueError(f"wfagpu_amd_configure_affine2p_wfadaptive rejected {tuple(pens)} under {tuple(wfadaptive)}")
         return
     if span is not None:      # (a Span, a dict of its fields or a 4-tuple; wfagpu_amd_configure_affine2p_span: the penalties run ends-free under it)
         if lib.wfagpu_amd_configure_affine2p_span(C.byref(Penalties2p(*[int(v) for v in pens])), C.byref(_as_span(span))) != 0:
@@ -593,7 +608,8 @@ class DeviceAligner:
         `penalties` is ignored then.  With a span too: two pieces ends-free (wfagpu_amd_align_device_2p_span), fetch_ends as under a
         span alone.
         wfadaptive: (min_wavefront_length, max_distance_threshold, steps_between_cutoffs), WFA2's wf-adaptive heuristic
-        (wfagpu_amd_align_device_adaptive; end to end, gap-affine: a band, a span or two pieces is an error).
+        (wfagpu_amd_align_device_adaptive; end to end: a band or a span is an error).  With affine2p too: the heuristic under two-piece
+        penalties (wfagpu_amd_align_device_2p_adaptive).
         linear: ("edit",), ("indel",) or ("linear", x, g), an edit, indel or gap-linear metric (wfagpu_amd_align_device_linear; exact
         search on one-component kernels: a band, two pieces or the heuristic is an error); `penalties` is ignored then.  With a span too:
         the metric ends-free (wfagpu_amd_align_device_linear_span), fetch_ends as under a span alone."""
@@ -608,8 +624,8 @@ class DeviceAligner:
         span = _as_span(span)
         if affine2p is not None and band > 0 and band_width > 0:
             raise ValueError("two-piece penalties are not combined with the adaptive band")
-        if wfadaptive is not None and (span is not None or affine2p is not None or (band > 0 and band_width > 0)):
-            raise ValueError("the wf-adaptive heuristic is not combined with an ends-free span, two-piece penalties or the adaptive band")
+        if wfadaptive is not None and (span is not None or (band > 0 and band_width > 0)):
+            raise ValueError("the wf-adaptive heuristic is not combined with an ends-free span or the adaptive band")
         if linear is not None and (affine2p is not None or wfadaptive is not None or (band > 0 and band_width > 0)):
             raise ValueError("an edit, indel or gap-linear metric is not combined with two-piece penalties, the heuristic or the adaptive band")
         d_ends = None
@@ -628,6 +644,10 @@ class DeviceAligner:
         elif linear is not None:
             rc = self.lib.wfagpu_amd_align_device_linear(self.ctx, C.byref(batch), C.byref(_as_linear(linear)), int(max_error),
                                                          bool(compute_cigar), d_scores.data_ptr(), C.byref(t), C.byref(o), C.byref(l))
+        elif wfadaptive is not None and affine2p is not None:
+            rc = self.lib.wfagpu_amd_align_device_2p_adaptive(self.ctx, C.byref(batch), C.byref(Penalties2p(*[int(v) for v in affine2p])), int(max_error),
+                                                              C.byref(WfAdaptive(*[int(v) for v in wfadaptive])), bool(compute_cigar), d_scores.data_ptr(),
+                                                              C.byref(t), C.byref(o), C.byref(l))
         elif wfadaptive is not None:
             rc = self.lib.wfagpu_amd_align_device_adaptive(self.ctx, C.byref(batch), pen, int(max_error), C.byref(WfAdaptive(*[int(v) for v in wfadaptive])),
                                                            bool(compute_cigar), d_scores.data_ptr(), C.byref(t), C.byref(o), C.byref(l))

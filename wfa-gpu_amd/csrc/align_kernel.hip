@@ -66,6 +66,7 @@
 //   align/loop_careful.inc    the careful score step (WFA2 to the letter)
 //   align/loop_careful_2p.inc the careful score step of the two-piece instantiations
 //   align/loop_careful_ad.inc the careful score step of the wf-adaptive instantiations (WFA2's heuristic cut-off)
+//   align/loop_careful_2pad.inc the careful score step of the wf-adaptive instantiations under two-piece penalties
 //   align/loop_careful_lin.inc the careful score step of the one-component instantiations (edit, indel, gap-linear), cells included
 //   align/band_window.inc, align/loop_banded.inc   the adaptive band: the reference's window rule, the banded search
 #include <type_traits>
@@ -208,6 +209,10 @@ __device__ __forceinline__ ColdParams cold_params() {
 // (wavefront_heuristic.c:508-561).  A heuristic's rows depend on every cell WFA2 computes, so neither the window nor the reach
 // interval prunes: a row is bounded by the sequences and by the ring (|k| <= (s - o) / e up to score s), M carries WFA2's trimmed
 // limits; a score step of its own (align/loop_careful_ad.inc), origin bytes in ROWS.
+// ADAPTIVE && TWOPIECE (align_kernel_2pad.hip includes this file for those instantiations): the heuristic on the five-component ring of
+// TWOPIECE -- the cut-off equates I1, D1, I2 and D2 to M's limits (wavefront_heuristic.c:549-560); a ring of |k| <= R(s), the longest gap
+// a score pays for under either piece (wfa_reach2p); a score step of its own (align/loop_careful_2pad.inc) with a reduction slot of 12
+// words per score (ten limits and the distance), origin bytes in ROWS.  DESIGN.md section 4.15.
 // LINEAR (align_kernel_lin.hip includes this file for those instantiations): WFA2's edit, indel and gap_linear distances -- mismatch x,
 // every gap base g (carried as e = oe = g), no mismatch move under indel (x == WFA_LIN_NO_MISMATCH: a kernel argument, wave-uniform).  One component per score: a
 // ring of max(x, g) + 1 rows of M and nothing else (de == 0), no run-limit row, I / D entries of the row book never set; a score step
@@ -226,7 +231,7 @@ wfa_align_kernel(const WfaAlignParams p) {
   static_assert(!HYBRID || (!GLOBAL_RING && !BANDED), "the hybrid ring is an exact LDS tier");
   static_assert(!ENDSFREE || (!BANDED && !HYBRID && !TIMED), "ends-free: the exact search of tiers 0, 1, 2 and 3");
   static_assert(!TWOPIECE || (!BANDED && !HYBRID && !TIMED), "two pieces: the exact search of tiers 0, 1, 2 and 3, end to end or ends-free");
-  static_assert(!ADAPTIVE || (!BANDED && !HYBRID && !TIMED && !ENDSFREE && !TWOPIECE), "wf-adaptive: end to end, gap-affine, tiers 0, 1, 2 and 3");
+  static_assert(!ADAPTIVE || (!BANDED && !HYBRID && !TIMED && !ENDSFREE), "wf-adaptive: end to end, gap-affine or two pieces, tiers 0, 1, 2 and 3");
   static_assert(!LINEAR || (!BANDED && !HYBRID && !TIMED && !TWOPIECE && !ADAPTIVE), "one component: the exact search of tiers 0, 1, 2 and 3, end to end or ends-free");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NT = NW * 64;
@@ -275,7 +280,9 @@ wfa_align_kernel(const WfaAlignParams p) {
   uint32_t* Tw = Pw + p.seq_words_cap;
   const int bkm = p.book_mask;                                // row book: 64 (or more) entries indexed by score & bkm
   int* red = reinterpret_cast<int*>(Tw + p.seq_words_cap);    // [3][8] per-score reduction slots (NW > 1)
-  uint32_t* bslot = reinterpret_cast<uint32_t*>(red + 24);    // [2] broadcast slots
+  // (ADAPTIVE && TWOPIECE: ten limits and the distance per score -- [3][12] for these instantiations alone)
+  constexpr int RED_W = (ADAPTIVE && TWOPIECE) ? 12 : 8;
+  uint32_t* bslot = reinterpret_cast<uint32_t*>(red + 3 * RED_W);    // [2] broadcast slots
   // "A cell of this score touched a sequence end" (multi-wave lean loops): one LDS word PER SCORE PARITY, set by the waves that see it,
   // read by every wave behind the score's barrier.  With a single sticky word a wave that is already computing score s + 1 could set it
   // before a slower wave had done its read for score s -- the waves would then leave the loop at different scores with their barrier
@@ -298,7 +305,8 @@ wfa_align_kernel(const WfaAlignParams p) {
   else { book2.I = book.D + (bkm + 1); book2.D = book2.I + (bkm + 1); }
   // (ADAPTIVE, NW > 1) [3][2] reduction slots of the cut-off's scan, behind the row book: rotated and reset like `red`
   int* red2 = nullptr;
-  if constexpr (ADAPTIVE && NW > 1) red2 = book.D + (bkm + 1);
+  if constexpr (ADAPTIVE && TWOPIECE && NW > 1) red2 = book2.D + (bkm + 1);
+  else if constexpr (ADAPTIVE && NW > 1) red2 = book.D + (bkm + 1);
 
   uint32_t chunk_cur = 0, chunk_left = 0;   // arena units owned by this block
   uint32_t dbg_i = 0;                       // (TIMED: barrier records written by this wave so far)
@@ -376,13 +384,21 @@ wfa_align_kernel(const WfaAlignParams p) {
       // up at least one base of the plen + tlen there are -- a gap base one, for at most o + e; a mismatch two, for x -- so no answer
       // costs more than max(x, o + e) (plen + tlen).  It bounds the row table.)
       if constexpr (ADAPTIVE) worst = (long long)max(x, oe) * ((long long)plen + tlen);
+      // (under two pieces: a gap base for at most max(o1 + e1, o2 + e2))
+      if constexpr (ADAPTIVE && TWOPIECE) worst = (long long)max(x, max(oe, oe2)) * ((long long)plen + tlen);
       // (LINEAR: a mismatch, or an insertion and a deletion where those cost less -- always so under indel, whose x is out of reach)
       if constexpr (LINEAR) worst = (long long)min(x, 2 * e) * min(plen, tlen) + (long long)e * abs(kend);
       budget = (int)min((long long)budget, worst);
     }
     int wlo = -plen, whi = tlen;
     bool feasible = true;
-    if constexpr (ADAPTIVE) {
+    if constexpr (ADAPTIVE && TWOPIECE) {
+      // wf-adaptive under two pieces: no pruning.  Up to score s no row leaves |k| <= R(s), the longest gap s pays for under
+      // min(o1 + n e1, o2 + n e2) (wfa_reach2p: a diagonal further out needs a longer gap, or several that cost more -- g is
+      // subadditive); a ring of that many diagonals on either side of 0 holds every row up to the budget; the score step checks it.
+      const long long kmax = wfa_reach2p(budget, oe, e, oe2, e2);
+      wlo = -(int)min((long long)plen, kmax); whi = (int)min((long long)tlen, kmax);
+    } else if constexpr (ADAPTIVE) {
       // wf-adaptive: no pruning.  Up to score s WFA2's rows stay within |k| <= (s - o) / e (a diagonal further out needs one more gap
       // base), so a ring of that many diagonals on either side of 0 holds every row up to the budget; the score step checks it.
       const long long kmax = budget >= oe ? ((long long)budget - (oe - e)) / e : 0;
@@ -549,7 +565,8 @@ wfa_align_kernel(const WfaAlignParams p) {
         if constexpr (BOOK_NW == 1) book2.reset();
         else { for (int i = tid; i <= bkm; i += NT) { book2.I[i] = book2.D[i] = ROW_NONE_A; } }
       }
-      if constexpr (NW > 1) { if (tid < 24) red[tid] = (tid & 7) == 6 ? 0 : (((tid & 7) & 1) ? INT_MIN : INT_MAX); }
+      if constexpr (ADAPTIVE && TWOPIECE) { if constexpr (NW > 1) { if (tid < 3 * RED_W) { const int j = tid % RED_W; red[tid] = j == RED_W - 1 ? 0 : (((j & 1) || j == 10) ? INT_MIN : INT_MAX); } } }
+      else if constexpr (NW > 1) { if (tid < 24) red[tid] = (tid & 7) == 6 ? 0 : (((tid & 7) & 1) ? INT_MIN : INT_MAX); }
       if constexpr (ADAPTIVE && NW > 1) { if (tid < 6) red2[tid] = (tid & 1) ? INT_MIN : INT_MAX; }
       block_sync<NW>();
 
@@ -753,7 +770,9 @@ wfa_align_kernel(const WfaAlignParams p) {
       bool touched_ever = ENDSFREE || TWOPIECE || touched_at_0 || cold_params()->no_lean != 0;    // (WFAGPU_NO_LEAN: the lean path is never entered)
       // ---- score loop ----------------------------------------------------------------------------
       if (!done && status == WFA_ST_DONE) for (;;) {
-        if constexpr (TWOPIECE) {
+        if constexpr (TWOPIECE && ADAPTIVE) {
+          #include "align/loop_careful_2pad.inc"
+        } else if constexpr (TWOPIECE) {
           #include "align/loop_careful_2p.inc"
         } else if constexpr (ADAPTIVE) {
           #include "align/loop_careful_ad.inc"
@@ -821,7 +840,49 @@ int occ_inst(size_t lds) {
   return nb;
 }
 
-#if defined(WFA_ALIGN_2PEF_UNIT)
+#if defined(WFA_ALIGN_2PAD_UNIT)
+// ---- the translation unit of the wf-adaptive heuristic under two-piece penalties (align_kernel_2pad.hip): tiers 0, 1, 2 and 3, with and without backtrace, packed and byte-compare
+template <bool BT, bool RAW>
+void launch_tier_2pad(const WfaAlignParams& p, int tier, size_t lds, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  switch (tier) {
+    case 0: launch_inst<1, BT, int16_t, false, RAW, false, false, 8, false, false, true, true>(p, lds, grid, stream, ev0, ev1); break;
+    case 1: launch_inst<4, BT, int16_t, false, RAW, false, false, 8, false, false, true, true>(p, lds, grid, stream, ev0, ev1); break;
+    case 2: launch_inst<16, BT, int16_t, false, RAW, false, false, 8, false, false, true, true>(p, lds, grid, stream, ev0, ev1); break;
+    default:
+      if (p.ring16) launch_inst<16, BT, int16_t, true, RAW, false, false, 8, false, false, true, true>(p, lds, grid, stream, ev0, ev1);
+      else launch_inst<16, BT, int32_t, true, RAW, false, false, 8, false, false, true, true>(p, lds, grid, stream, ev0, ev1);
+      break;
+  }
+}
+template <bool BT, bool RAW>
+int occ_tier_2pad(int tier, size_t lds) {
+  switch (tier) {
+    case 0: return occ_inst<1, BT, int16_t, false, RAW, false, false, 8, false, true, true>(lds);
+    case 1: return occ_inst<4, BT, int16_t, false, RAW, false, false, 8, false, true, true>(lds);
+    case 2: return occ_inst<16, BT, int16_t, false, RAW, false, false, 8, false, true, true>(lds);
+    default: return occ_inst<16, BT, int32_t, true, RAW, false, false, 8, false, true, true>(lds);
+  }
+}
+
+}  // namespace
+
+void wfa_launch_align_2pad(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  wfa_unit_entered(WFA_UNIT_ALIGN_2PAD);
+  const size_t lds = wfa_align_lds_bytes(p, tier);
+  if (with_bt) { if (raw) launch_tier_2pad<true, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_2pad<true, false>(p, tier, lds, grid, stream, ev0, ev1); }
+  else { if (raw) launch_tier_2pad<false, true>(p, tier, lds, grid, stream, ev0, ev1); else launch_tier_2pad<false, false>(p, tier, lds, grid, stream, ev0, ev1); }
+}
+
+int wfa_align_2pad_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds) {
+  wfa_unit_entered(WFA_UNIT_ALIGN_2PAD);
+  if (with_bt) return raw ? occ_tier_2pad<true, true>(tier, lds) : occ_tier_2pad<true, false>(tier, lds);
+  return raw ? occ_tier_2pad<false, true>(tier, lds) : occ_tier_2pad<false, false>(tier, lds);
+}
+
+// (this code object is loaded by the first launch of one of its kernels: wfagpu_amd_prime does that only under two-piece penalties configured with the heuristic)
+namespace { __global__ void k_prime_align_2pad() {} }
+void wfa_prime_align_2pad(hipStream_t stream) { wfa_unit_entered(WFA_UNIT_ALIGN_2PAD); hipLaunchKernelGGL(k_prime_align_2pad, dim3(1), dim3(64), 0, stream); }
+#elif defined(WFA_ALIGN_2PEF_UNIT)
 // ---- the translation unit of two-piece penalties under a span (align_kernel_2pef.hip): tiers 0, 1, 2 and 3, with and without
 // backtrace, packed and byte-compare
 template <bool BT, bool RAW>
@@ -1151,10 +1212,10 @@ size_t wfa_align_lds_bytes(const WfaAlignParams& p, int tier) {
   if (tier == 4) ring = (((size_t)(p.dm + p.de) * p.rs * sizeof(int16_t)) + 15) & ~(size_t)15;       // hybrid: M and I rings
   else if (tier != 3) ring = (((size_t)(p.dm + 2 * p.de + 2 * p.de2 + ((tier == 0 && p.band_width <= 0 && p.de > 0) ? 1 : 0)) * p.rs * sizeof(int16_t)) + 15) & ~(size_t)15;     // (+ the run-limit row of the one-wave exact kernels; not the one-component ones)
   const size_t seq = (size_t)2 * p.seq_words_cap * 4;
-  // reduction slots [24] + broadcast [2] + (NW > 1) row book [3][book]
+  // reduction slots [24] (wf-adaptive under two pieces: [36], twelve words per score) + broadcast [2] + (NW > 1) row book [3][book]
   const size_t bk = (size_t)p.book_mask + 1;
   // (wf-adaptive, p.ad_steps > 0: eight words more behind the book, the reduction slots of the cut-off's scan)
-  const size_t meta = (size_t)(24 + 2 + ((tier == 0 || p.band_width > 0) ? 0 : (p.e2 > 0 ? 5 : 3) * bk + (p.ad_steps > 0 ? 8 : 0))) * 4;    // (tiers 1, 2, 3, 4 of the exact search: row book in LDS; two pieces: I2 and D2 too)
+  const size_t meta = (size_t)(((p.e2 > 0 && p.ad_steps > 0) ? 36 : 24) + 2 + ((tier == 0 || p.band_width > 0) ? 0 : (p.e2 > 0 ? 5 : 3) * bk + (p.ad_steps > 0 ? 8 : 0))) * 4;    // (tiers 1, 2, 3, 4 of the exact search: row book in LDS; two pieces: I2 and D2 too)
   return ((ring + seq + meta) + 15) & ~(size_t)15;
 }
 

@@ -487,7 +487,10 @@ __device__ __forceinline__ void finish_pair(const WfaTraceParams& p, const size_
   // difference would mean a broken trace).  Adaptive band: a path may open two gaps back to back
   // where the extension cell had left the band; printed, they are one gap and cost less -- the
   // reported score follows the alignment that is returned.
-  if (cost != score) {
+  // (TRACE_2P under the heuristic: less is what a gap walked on the first piece prints as -- WfaTraceParams::cost_below_score_ok)
+  bool differs = cost != score;
+  if constexpr (TRACE_2P) { if (p.cost_below_score_ok && cost < score) differs = false; }
+  if (differs) {
     if (p.score_fix) p.score_fix[pair] = cost;
     else p.cigar_len[pair] = 0xFFFFFFFFu;
   }
@@ -943,7 +946,9 @@ __global__ void __launch_bounds__(TRACE_THREADS) wfa_trace_wave_kernel(const Wfa
       if (lane == 0) {
         p.cigar_off[pair] = txt_off;
         p.cigar_len[pair] = len;
-        if (cost != score) {
+        bool differs = cost != score;
+        if constexpr (TRACE_2P) { if (p.cost_below_score_ok && cost < score) differs = false; }
+        if (differs) {
           if (p.score_fix) p.score_fix[pair] = cost;
           else p.cigar_len[pair] = 0xFFFFFFFFu;
         }

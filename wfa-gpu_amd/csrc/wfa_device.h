@@ -239,6 +239,10 @@ struct WfaTraceParams {
   int extra_items;               // RLE items a text may have beyond 2 * operations + 1 (the two free runs): sizes the upper-bound text slots
   int oe2, e2;                   // two-piece gap-affine (wfa_launch_trace_2p only): the second piece; origin bytes are BT2_*
   // (wfa_launch_trace_lin: oe == e is the cost of a gap base, origin bytes are BTL_*)
+  // (wfa_launch_trace_2p only) 1: two pieces under the wf-adaptive heuristic.  The cut-off may have dropped the I2 / D2 cells a long gap
+  // would have run on, so the path carries it on the first piece; printed, it is one run, priced by the cheaper piece: the text may cost
+  // LESS than the wavefront score.  The score stands, as WFA2 reports it; a text that costs MORE is still a broken trace.
+  int cost_below_score_ok;
 };
 
 // Host-side launchers (one per translation unit).
@@ -329,6 +333,18 @@ void wfa_prime_align_2pef(hipStream_t stream);
 // lane of launch_alignments* -- wants its two-piece penalties to run under (nullptr: end to end).
 bool wfa_configured_affine2p_span(int* out4);
 const int* wfa_lane_affine2p_span4();
+// The instantiations for the wf-adaptive heuristic under two-piece penalties (align_kernel_2pad.hip: a code object of their own, loaded
+// only by such calls): tiers 0, 1, 2 and 3, careful loop with WFA2's cut-off over five components, origin bytes in ROWS; the two-piece
+// backtrace kernels serve them as they are.  wfa_align_lds_bytes serves them too (WfaAlignParams::e2 > 0 and ad_steps > 0).
+void wfa_launch_align_2pad(const WfaAlignParams& p, int tier, bool with_bt, bool raw, int grid, hipStream_t stream,
+                           hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+int wfa_align_2pad_max_blocks_per_cu(int tier, bool with_bt, bool raw, size_t lds_bytes);
+void wfa_prime_align_2pad(hipStream_t stream);
+// The pair of wfagpu_amd_configure_affine2p_wfadaptive (wfa_launch.hip): false when none is configured; out (optional) receives
+// {x, o1, e1, o2, e2, min_wavefront_length, max_distance_threshold, steps_between_cutoffs}.  wfa_lane_affine2p_wfadaptive8: what the
+// calling thread -- a lane of launch_alignments* -- wants its wfagpu_amd_align_device call to run under (nullptr: something else).
+bool wfa_configured_affine2p_wfadaptive(int* out8);
+const int* wfa_lane_affine2p_wfadaptive8();
 // The span that wfagpu_amd_configure_linear_span set with its metric (wfa_launch.hip): false when the configured metric runs end to
 // end, or none is configured; out (optional) receives the four members.  wfa_lane_linear_span4: the span the calling thread -- a lane
 // of launch_alignments* -- wants its metric to run under (nullptr: end to end).
@@ -381,7 +397,7 @@ const WfaShortEntry* wfa_short_ef_entry_e4(int ascii, int bt, int li, int idx);
 // Which of the optional code objects -- the ones only some callers load -- this process has entered: every host function that launches,
 // queries or primes a kernel of such a unit says so (the runtime loads a code object at the first of these).  Process-wide, never
 // cleared; wfagpu_amd_debug_code_objects() (wfa_host.hip) hands the bits out, tests check "never loaded" with them.
-enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u, WFA_UNIT_ALIGN_AD = 8u, WFA_UNIT_ALIGN_LIN = 16u, WFA_UNIT_TRACE_LIN = 32u, WFA_UNIT_ALIGN_LINEF = 64u, WFA_UNIT_SHORT_LIN = 128u, WFA_UNIT_SHORT_LINEF = 256u, WFA_UNIT_SHORT_EF = 512u, WFA_UNIT_ALIGN_2PEF = 1024u };
+enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u, WFA_UNIT_ALIGN_AD = 8u, WFA_UNIT_ALIGN_LIN = 16u, WFA_UNIT_TRACE_LIN = 32u, WFA_UNIT_ALIGN_LINEF = 64u, WFA_UNIT_SHORT_LIN = 128u, WFA_UNIT_SHORT_LINEF = 256u, WFA_UNIT_SHORT_EF = 512u, WFA_UNIT_ALIGN_2PEF = 1024u, WFA_UNIT_ALIGN_2PAD = 2048u };
 void wfa_unit_entered(unsigned unit);
 // Code-object priming: one empty launch per kernel translation unit (see the definitions).
 void wfa_prime_pack(hipStream_t stream);

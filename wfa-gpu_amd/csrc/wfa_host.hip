@@ -513,6 +513,8 @@ int wfagpu_amd_prime(wfagpu_amd_ctx_t* c) {
   // (the two-piece kernels: only callers under such penalties -- the ends-free ones where they were configured with a span)
   if (wfa_configured_affine2p(nullptr)) { if (wfa_configured_affine2p_span(nullptr)) wfa_prime_align_2pef(c->stream); else wfa_prime_align_2p(c->stream); wfa_prime_trace_2p(c->stream); }
   if (wfa_configured_wfadaptive(nullptr)) wfa_prime_align_ad(c->stream);      // (the wf-adaptive kernels: only callers under the heuristic)
+  // (the heuristic under two pieces -- wfagpu_amd_configure_affine2p_wfadaptive --: its wavefront kernels and the two-piece backtrace)
+  if (wfa_configured_affine2p_wfadaptive(nullptr)) { wfa_prime_align_2pad(c->stream); wfa_prime_trace_2p(c->stream); }
   // (the one-component kernels: only callers under such a metric -- the ends-free ones where it was configured with a span)
   if (wfa_configured_linear(nullptr)) {
     if (wfa_configured_linear_span(nullptr)) { wfa_prime_align_linef(c->stream); wfa_prime_short_linef(c->stream); } else { wfa_prime_align_lin(c->stream); wfa_prime_short_lin(c->stream); }
@@ -570,6 +572,14 @@ int window_width_ad(long long S, int o, int e, unsigned max_seq_len) {
   return (int)std::max<long long>(1, std::min<long long>(all, 2 * (S >= o + e ? (S - o) / e : 0) + 1));
 }
 
+// The same under the heuristic with two-piece penalties: nothing is pruned, up to score S no row leaves |k| <= R(S), the longest gap S
+// pays for under min(o1 + n e1, o2 + n e2) (wfa_reach2p; a diagonal further out needs a longer gap, or several that cost more).
+int window_width_2pad(long long S, const WfaAlignParams& p, unsigned max_seq_len) {
+  const long long all = 2ll * max_seq_len + 1;
+  if (S >= INT_MAX / 2) return (int)all;
+  return (int)std::max<long long>(1, std::min<long long>(all, 2 * wfa_reach2p(S, p.oe, p.e, p.oe2, p.e2) + 1));
+}
+
 // Smallest tier whose LDS footprint fits a score budget S.
 // few_pairs: the list is expected to hold fewer pairs than the device has workgroup slots (the re-run of a long-read batch's
 // budget misses): what counts is the latency of ONE alignment, so wide wavefronts take sixteen waves instead of four.
@@ -618,13 +628,15 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   // Two pieces under a span (p.e2 > 0 and p.ends: align_kernel_2pef.hip): rings with the two-piece row counts, window_width_2p widened by
   // the free bases like the gap-affine span -- the kernel's window is the stray of the budget on either side of the hull of the start
   // and end diagonals, and the hull is at most the free bases wider than [min(0, kend), max(0, kend)].
-  // wf-adaptive (p.ad_steps > 0): tiers 0, 1, 2 and 3 likewise, rings sized by window_width_ad; never combined with either.
+  // wf-adaptive (p.ad_steps > 0): tiers 0, 1, 2 and 3 likewise, rings sized by window_width_ad; never combined with a span.
+  // wf-adaptive under two pieces (p.ad_steps > 0 and p.e2 > 0: align_kernel_2pad.hip): rings with the two-piece row counts, sized by
+  // window_width_2pad; tiers 0, 1, 2 and 3, no tier 5, no band, no budgets from a sample.
   // One component (p.de == 0: edit, indel, gap-linear): tiers 0, 1, 2 and 3 likewise.  Its window -- (S / g - |kend|) / 2 diagonals on
   // either side of the end diagonals -- is widest at |kend| = S / g: S / g + 1 diagonals, which is window_width with o = 0; its ring is
   // dm rows and nothing else (de == 0), which wfa_align_lds_bytes sees: a pair that needs four waves under gap-affine may fit one here.
   // One component under a span (p.de == 0 and p.ends: align_kernel_linef.hip): that bound widened by the free bases, as for the gap-affine span.
   const bool ef = p.ends != nullptr, tp2 = p.e2 > 0, ad = p.ad_steps > 0, lin = p.de == 0;
-  int width = ad ? window_width_ad(max_score, p.oe - p.e, p.e, max_seq_len) : tp2 ? window_width_2p(max_score, p, max_seq_len) : window_width(max_score, p.oe - p.e, p.e, max_seq_len);
+  int width = (ad && tp2) ? window_width_2pad(max_score, p, max_seq_len) : ad ? window_width_ad(max_score, p.oe - p.e, p.e, max_seq_len) : tp2 ? window_width_2p(max_score, p, max_seq_len) : window_width(max_score, p.oe - p.e, p.e, max_seq_len);
   if (ef) {
     const long long m = max_seq_len;
     const long long free_sum = std::min<long long>(p.span_pbf, m) + std::min<long long>(p.span_pef, m) + std::min<long long>(p.span_tbf, m) + std::min<long long>(p.span_tef, m);
@@ -713,7 +725,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     if (t == 0 && (width > 1024 || p.dm > 64)) continue;
     if (t == 1 && width > 8192) continue;
     if (t == 1 && few_pairs && width >= 1024 && !min_tier && wfa_align_lds_bytes(p, 2) <= budget[2]) continue;
-    int nb = (lin && ef) ? wfa_align_linef_max_blocks_per_cu(t, bt, raw, lds) : (tp2 && ef) ? wfa_align_2pef_max_blocks_per_cu(t, bt, raw, lds) : lin ? wfa_align_lin_max_blocks_per_cu(t, bt, raw, lds) : ad ? wfa_align_ad_max_blocks_per_cu(t, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(t, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(t, bt, raw, lds) : wfa_align_max_blocks_per_cu(t, bt, raw, false, lds);
+    int nb = (lin && ef) ? wfa_align_linef_max_blocks_per_cu(t, bt, raw, lds) : (tp2 && ef) ? wfa_align_2pef_max_blocks_per_cu(t, bt, raw, lds) : lin ? wfa_align_lin_max_blocks_per_cu(t, bt, raw, lds) : (ad && tp2) ? wfa_align_2pad_max_blocks_per_cu(t, bt, raw, lds) : ad ? wfa_align_ad_max_blocks_per_cu(t, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(t, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(t, bt, raw, lds) : wfa_align_max_blocks_per_cu(t, bt, raw, false, lds);
     if (nb < 1) continue;
     // Occupancy-matched instantiation of the one-wave kernels: LDS decides how many rings a CU holds; compiled for 8 waves
     // per SIMD the kernel lives on 64 VGPRs and 78 SGPRs (123 scalar spills + scratch), which only pays when 8 waves per
@@ -757,7 +769,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   p.rs = rs_plain;
   const size_t lds = wfa_align_lds_bytes(p, 3);
   if (lds > c->lds_per_block_max) return false;   // sequences themselves do not fit LDS
-  const int nb = (lin && ef) ? wfa_align_linef_max_blocks_per_cu(3, bt, raw, lds) : (tp2 && ef) ? wfa_align_2pef_max_blocks_per_cu(3, bt, raw, lds) : lin ? wfa_align_lin_max_blocks_per_cu(3, bt, raw, lds) : ad ? wfa_align_ad_max_blocks_per_cu(3, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(3, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(3, bt, raw, lds) : wfa_align_max_blocks_per_cu(3, bt, raw, false, lds);
+  const int nb = (lin && ef) ? wfa_align_linef_max_blocks_per_cu(3, bt, raw, lds) : (tp2 && ef) ? wfa_align_2pef_max_blocks_per_cu(3, bt, raw, lds) : lin ? wfa_align_lin_max_blocks_per_cu(3, bt, raw, lds) : (ad && tp2) ? wfa_align_2pad_max_blocks_per_cu(3, bt, raw, lds) : ad ? wfa_align_ad_max_blocks_per_cu(3, bt, raw, lds) : tp2 ? wfa_align_2p_max_blocks_per_cu(3, bt, raw, lds) : ef ? wfa_align_ef_max_blocks_per_cu(3, bt, raw, lds) : wfa_align_max_blocks_per_cu(3, bt, raw, false, lds);
   *out = {3, width, max_score, lds, std::max(1, std::min(nb, 2))};
   return true;
 }
@@ -793,6 +805,9 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
                              const wfagpu_amd_penalties2p_t* pen2 = nullptr, const wfagpu_amd_wfadaptive_t* wfad = nullptr,
                              const wfagpu_amd_linear_t* linm = nullptr) {
   if (!c || !b || !d_scores) return -1;
+  // pen2 and wfad together: the heuristic under two-piece penalties (align_kernel_2pad.hip), end to end.  Only
+  // wfagpu_amd_align_device_2p_adaptive and a lane under wfagpu_amd_configure_affine2p_wfadaptive hand in both: every other door
+  // takes one of the two, so the pair cannot be reached through them
   // linm != nullptr: an edit, indel or gap-linear metric (align_kernel_lin.hip: one component), exact search, end to end -- or, with a
   // span, ends-free (align_kernel_linef.hip: the two are combined through wfagpu_amd_align_device_linear_span alone); `pen` is ignored:
   // it becomes (x, 0, g) -- a gap base costs g, nothing opens -- for everything below that only sizes or bounds; indel: x = 2 g, what an
@@ -815,7 +830,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
   const bool tp2 = pen2 != nullptr;
   // wfad != nullptr: WFA2's wf-adaptive heuristic (align_kernel_ad.hip), end to end, gap-affine
   const bool ad = wfad != nullptr;
-  if (ad && (ef || tp2)) { fprintf(stderr, "[!] ERROR: the wf-adaptive heuristic is not combined with an ends-free span or two-piece penalties\n"); return -1; }
+  if (ad && ef) { fprintf(stderr, "[!] ERROR: the wf-adaptive heuristic is not combined with an ends-free span\n"); return -1; }
   if (ad && (wfad->min_wavefront_length < 1 || wfad->max_distance_threshold < 0 || wfad->steps_between_cutoffs < 1)) {
     fprintf(stderr, "[!] ERROR: wf-adaptive takes min_wavefront_length >= 1, max_distance_threshold >= 0, steps_between_cutoffs >= 1 (got %d,%d,%d)\n",
             wfad->min_wavefront_length, wfad->max_distance_threshold, wfad->steps_between_cutoffs);
@@ -951,6 +966,11 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
     // every g scores and the reach takes them back at the same rate: B^2 / (2 g) cells under a budget B)
     const double B = std::min<unsigned>(max_error, 2 * max_len);
     est_pair_bytes = 0.5 * (B + 1) * (B + 1) / pen.e + 16.0 * B + 4096.0;
+  } else if (ad && tp2) {
+    // (wf-adaptive under two pieces: one byte per cell of the un-pruned two-piece diamond -- a row gains a diagonal on each side every
+    // min(e1, e2) scores and loses none until the cut-off bites: B^2 / min(e1, e2) bytes under a budget B, refined after every pass)
+    const double B = std::min<unsigned>(max_error, 2 * max_len);
+    est_pair_bytes = (B + 1) * (B + 1) / std::min(pen.e, e2) + 16.0 * B + 4096.0;
   } else if (ad) {
     // (wf-adaptive: rows behind a row table in every tier; nothing is pruned, so until the cut-off bites a row gains two diagonals
     // every e scores and loses none: B^2 / e bytes under a budget B -- an upper estimate, refined after every pass)
@@ -1267,6 +1287,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
         else if (lin && ef) wfa_launch_align_linef(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else if (tp2 && ef) wfa_launch_align_2pef(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else if (ef) wfa_launch_align_ef(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
+        else if (tp2 && ad) wfa_launch_align_2pad(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else if (tp2) wfa_launch_align_2p(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else if (ad) wfa_launch_align_ad(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
         else if (lin) wfa_launch_align_lin(ap, tp.tier, cigar_now, raw, grid, st, L.e0, L.e1);
@@ -1307,7 +1328,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
       }
       // (whatever the budget, no optimal alignment costs more than mismatching the shorter sequence and one gap for the rest)
       // (wf-adaptive: the heuristic's answer may cost more; the kernel's bound: no alignment costs more than max(x, o + e) per base)
-      s_hi = std::min<long long>(s_hi, ad ? 2ll * std::max(pen.x, oe) * max_len : (long long)pen.x * max_len + oe + (long long)pen.e * max_len);
+      s_hi = std::min<long long>(s_hi, ad ? 2ll * std::max(std::max(pen.x, oe), o2 + e2) * max_len : (long long)pen.x * max_len + oe + (long long)pen.e * max_len);
       // ---- backtrace + CIGAR for everything of the chain's list that finished -----------------------------------------
       if (zero_counter(c, CT_SUM_OPS, 2)) return -1;
       if (zero_counter(c, CT_OPS)) return -1;
@@ -1363,6 +1384,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
         tp.packed = ap.packed; tp.meta = ap.meta; tp.work = chain_list; tp.n_work = n_chain;
         tp.x = pen.x; tp.oe = oe; tp.e = pen.e;
         tp.oe2 = ap.oe2; tp.e2 = ap.e2;
+        tp.cost_below_score_ok = (tp2 && ad) ? 1 : 0;
         tp.score = d_scores; tp.status = static_cast<const uint32_t*>(c->status.p);
         tp.score_fix = (want_band && !raw) ? d_scores : nullptr;
         tp.arena = ap.arena; tp.arena_bytes = (unsigned long long)c->arena.cap; tp.bt_final_row = ap.bt_final_row;
@@ -1732,6 +1754,13 @@ extern "C" int wfagpu_amd_align_device(wfagpu_amd_ctx_t* c, const wfagpu_amd_bat
     const wfagpu_amd_span_t span{ls[0], ls[1], ls[2], ls[3]};
     return align_device_impl(c, b, pen, max_error, band, band_width, compute_cigar, d_scores, d_text, d_off, d_len, &span, nullptr);
   }
+  // (two-piece penalties configured with the heuristic: wfagpu_amd_configure_affine2p_wfadaptive)
+  const int* const l8 = wfa_lane_affine2p_wfadaptive8();
+  if (l8) {
+    const wfagpu_amd_penalties2p_t p2{l8[0], l8[1], l8[2], l8[3], l8[4]};
+    const wfagpu_amd_wfadaptive_t h{l8[5], l8[6], l8[7]};
+    return align_device_impl(c, b, pen, max_error, band, band_width, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, &p2, &h);
+  }
   // (the same for configured two-piece penalties: wfagpu_amd_configure_affine2p)
   const int* const l2 = wfa_lane_affine2p5();
   if (l2) {
@@ -1793,6 +1822,14 @@ extern "C" int wfagpu_amd_align_device_2p(wfagpu_amd_ctx_t* c, const wfagpu_amd_
                                           const unsigned int** d_len) {
   if (!pens) { fprintf(stderr, "[!] ERROR: wfagpu_amd_align_device_2p needs penalties\n"); return -1; }
   return align_device_impl(c, b, affine_penalties_t{}, max_error, -1, 0, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, pens);
+}
+
+extern "C" int wfagpu_amd_align_device_2p_adaptive(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b, const wfagpu_amd_penalties2p_t* pens, int max_error,
+                                                   const wfagpu_amd_wfadaptive_t* heuristic, bool compute_cigar, int32_t* d_scores,
+                                                   const char** d_text, const unsigned long long** d_off, const unsigned int** d_len) {
+  if (!pens) { fprintf(stderr, "[!] ERROR: wfagpu_amd_align_device_2p_adaptive needs penalties\n"); return -1; }
+  // (NULL: the exact two-piece search)
+  return align_device_impl(c, b, affine_penalties_t{}, max_error, -1, 0, compute_cigar, d_scores, d_text, d_off, d_len, nullptr, nullptr, pens, heuristic);
 }
 
 extern "C" int wfagpu_amd_align_device_2p_span(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b, const wfagpu_amd_penalties2p_t* pens, int max_error,

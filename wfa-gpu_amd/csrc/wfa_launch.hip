@@ -76,7 +76,53 @@ thread_local const int* t_lane_lin = nullptr;
 bool g_lin_span_set = false;
 int g_lin_span[4] = {0, 0, 0, 0};
 thread_local const int* t_lane_lin_span = nullptr;
+// Two-piece penalties configured WITH the heuristic (wfagpu_amd_configure_affine2p_wfadaptive): a state of its own -- {x, o1, e1, o2, e2,
+// min_len, max_dist, steps}, never g_2p or g_ad, which stay the plain ones' --, handed over the same way
+// (wfa_lane_affine2p_wfadaptive8); under the same mutex: never configured together with any of the others.
+bool g_2pad_set = false;
+int g_2pad[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+thread_local const int* t_lane_2pad = nullptr;
 }  // namespace
+
+bool wfa_configured_affine2p_wfadaptive(int* out8) {
+  std::lock_guard<std::mutex> lock(g_span_mutex);
+  if (out8 && g_2pad_set) for (int i = 0; i < 8; ++i) out8[i] = g_2pad[i];
+  return g_2pad_set;
+}
+const int* wfa_lane_affine2p_wfadaptive8() { return t_lane_2pad; }
+
+extern "C" int wfagpu_amd_configure_affine2p_wfadaptive(const wfagpu_amd_penalties2p_t* pens, const wfagpu_amd_wfadaptive_t* h) {
+  const bool on = pens != nullptr && h != nullptr;
+  if (on && (pens->mismatch <= 0 || pens->gap_opening1 <= 0 || pens->gap_extension1 <= 0 || pens->gap_opening2 <= 0 || pens->gap_extension2 <= 0)) {
+    fprintf(stderr, "[!] ERROR: two-piece penalties must all be positive (got %d,%d,%d,%d,%d)\n", pens->mismatch, pens->gap_opening1, pens->gap_extension1,
+            pens->gap_opening2, pens->gap_extension2);
+    return -1;
+  }
+  if (on && (h->min_wavefront_length < 1 || h->max_distance_threshold < 0 || h->steps_between_cutoffs < 1)) {
+    fprintf(stderr, "[!] ERROR: wf-adaptive takes min_wavefront_length >= 1, max_distance_threshold >= 0, steps_between_cutoffs >= 1 (got %d,%d,%d)\n",
+            h->min_wavefront_length, h->max_distance_threshold, h->steps_between_cutoffs);
+    return -1;
+  }
+  std::lock_guard<std::mutex> lock(g_span_mutex);
+  if (on && (g_span_set || g_2p_set || g_ad_set || g_lin_set)) {
+    fprintf(stderr, "[!] ERROR: two-piece penalties with the wf-adaptive heuristic are not combined with an ends-free span, plain two-piece penalties, the plain heuristic or a metric (%s configured)\n",
+            g_span_set ? "a span is" : g_2p_set ? "such penalties are" : g_ad_set ? "the heuristic is" : "a metric is");
+    return -1;
+  }
+  g_2pad_set = on;
+  if (on) {
+    g_2pad[0] = pens->mismatch; g_2pad[1] = pens->gap_opening1; g_2pad[2] = pens->gap_extension1; g_2pad[3] = pens->gap_opening2; g_2pad[4] = pens->gap_extension2;
+    g_2pad[5] = h->min_wavefront_length; g_2pad[6] = h->max_distance_threshold; g_2pad[7] = h->steps_between_cutoffs;
+  }
+  return 0;
+}
+
+// (said by the four other configure calls while that pair is configured)
+static bool rejected_under_2pad(const char* what) {
+  if (!g_2pad_set) return false;
+  fprintf(stderr, "[!] ERROR: %s not combined with two-piece penalties under the wf-adaptive heuristic (they are configured)\n", what);
+  return true;
+}
 
 bool wfa_configured_linear(int* out3) {
   std::lock_guard<std::mutex> lock(g_span_mutex);
@@ -105,6 +151,7 @@ static int configure_linear_impl(const wfagpu_amd_linear_t* m, const wfagpu_amd_
     return -1;
   }
   std::lock_guard<std::mutex> lock(g_span_mutex);
+  if (m && rejected_under_2pad("an edit, indel or gap-linear metric is")) return -1;
   if (m && (g_span_set || g_2p_set || g_ad_set)) {
     fprintf(stderr, "[!] ERROR: an edit, indel or gap-linear metric is not combined with an ends-free span, two-piece penalties or the wf-adaptive heuristic (%s configured)\n",
             g_span_set ? "a span is" : g_2p_set ? "such penalties are" : "it is");
@@ -135,6 +182,7 @@ extern "C" int wfagpu_amd_configure_wfadaptive(const wfagpu_amd_wfadaptive_t* h)
     return -1;
   }
   std::lock_guard<std::mutex> lock(g_span_mutex);
+  if (h && rejected_under_2pad("the wf-adaptive heuristic is")) return -1;
   if (h && g_lin_set) {
     fprintf(stderr, "[!] ERROR: the wf-adaptive heuristic is not combined with an edit, indel or gap-linear metric (one is configured)\n");
     return -1;
@@ -182,6 +230,7 @@ static int configure_affine2p_impl(const wfagpu_amd_penalties2p_t* pens, const w
     return -1;
   }
   std::lock_guard<std::mutex> lock(g_span_mutex);
+  if (pens && rejected_under_2pad("two-piece penalties are")) return -1;
   if (pens && g_span_set) {
     fprintf(stderr, "[!] ERROR: two-piece penalties are not combined with an ends-free span (one is configured)\n");
     return -1;
@@ -212,6 +261,7 @@ extern "C" int wfagpu_amd_configure_span(const wfagpu_amd_span_t* span) {
     return -1;
   }
   std::lock_guard<std::mutex> lock(g_span_mutex);
+  if (span && rejected_under_2pad("an ends-free span is")) return -1;
   if (span && g_2p_set) {
     fprintf(stderr, "[!] ERROR: an ends-free span is not combined with two-piece penalties (they are configured)\n");
     return -1;
@@ -358,14 +408,17 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
   const int* const span = wfa_configured_span(sp4) ? sp4 : nullptr;
   // (under configured two-piece penalties: a gap run priced by the cheaper piece, the score checked against the five-table program)
   int q5[5] = {0, 0, 0, 0, 0};
-  const int* const p2 = wfa_configured_affine2p(q5) ? q5 : nullptr;
+  // (two-piece penalties configured with the heuristic: priced and scored as two pieces, judged as under the heuristic)
+  int q8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const bool under_2pad = wfa_configured_affine2p_wfadaptive(q8);
+  const int* const p2 = wfa_configured_affine2p(q5) ? q5 : under_2pad ? q8 : nullptr;
   // (two-piece penalties configured with a span: the text priced without its free runs, each paid run by the cheaper piece, the score
   // checked against the five-table program with free borders)
   int ps4[4] = {0, 0, 0, 0};
   const int* const p2span = (p2 && wfa_configured_affine2p_span(ps4)) ? ps4 : nullptr;
   // (under a configured wf-adaptive heuristic: the CIGAR is valid and costs the score as always; the score may lie ABOVE the CPU
   // scorer's optimum -- such pairs are counted and said, they are no failures; a score below the optimum is one)
-  const bool heuristic = wfa_configured_wfadaptive(nullptr);
+  const bool heuristic = wfa_configured_wfadaptive(nullptr) || under_2pad;
   // (under a configured edit, indel or gap-linear metric: the CIGAR priced under the metric -- an X under indel is a failure --, the
   // score checked against the one-table program; the penalties of the options are not looked at)
   int m3[3] = {0, 0, 0};
@@ -394,6 +447,7 @@ int check_batch(const CallArgs& a, size_t from, size_t to, int batch_idx, unsign
           const bool c2 = lspan ? check_linear_distance_span(text, pattern, m.text_len, m.pattern_len, dist, lm[0], lm[1], lm[2], cg, lspan)
                         : lm ? check_linear_distance(text, pattern, m.text_len, m.pattern_len, dist, lm[0], lm[1], lm[2], cg)
                         : p2span ? check_affine2p_distance_span(text, pattern, m.text_len, m.pattern_len, dist, p2[0], p2[1], p2[2], p2[3], p2[4], cg, p2span)
+                        : under_2pad ? check_affine2p_distance_heuristic(text, pattern, m.text_len, m.pattern_len, dist, p2[0], p2[1], p2[2], p2[3], p2[4], cg)
                         : p2 ? check_affine2p_distance(text, pattern, m.text_len, m.pattern_len, dist, p2[0], p2[1], p2[2], p2[3], p2[4], cg)
                         : span ? check_affine_distance_span(text, pattern, m.text_len, m.pattern_len, dist, a.opt.penalties.x,
                                                             a.opt.penalties.o, a.opt.penalties.e, cg, span)
@@ -1126,6 +1180,14 @@ int run_device(const CallArgs& a, Shard& sh) {
         if (!warned3.exchange(true)) fprintf(stderr, "[!] WARNING: the adaptive band is not combined with the wf-adaptive heuristic: running under the heuristic alone\n");
       }
       t_lane_ad = under_ad ? h3 : nullptr;
+      // (and for two-piece penalties configured with the heuristic -- wfagpu_amd_configure_affine2p_wfadaptive --: a band is not used, said once)
+      int h8[8];
+      const bool under_2pad = wfa_configured_affine2p_wfadaptive(h8);
+      if (under_2pad && a.opt.band > 0 && a.opt.threads_per_block > 0) {
+        static std::atomic<bool> warned5{false};
+        if (!warned5.exchange(true)) fprintf(stderr, "[!] WARNING: the adaptive band is not combined with two-piece penalties under the wf-adaptive heuristic: running without the band\n");
+      }
+      t_lane_2pad = under_2pad ? h8 : nullptr;
       // (and for a configured edit, indel or gap-linear metric -- wfagpu_amd_configure_linear --: the gap-affine penalties of the
       // options are ignored and a band is not used, said once)
       int m3[3];
@@ -1144,6 +1206,7 @@ int run_device(const CallArgs& a, Shard& sh) {
       t_lane_2p = nullptr;
       t_lane_2p_span = nullptr;
       t_lane_ad = nullptr;
+      t_lane_2pad = nullptr;
       t_lane_lin = nullptr;
       t_lane_lin_span = nullptr;
       if (arc) return arc;

@@ -72,6 +72,8 @@ static void usage(const char* prog) {
            "\t                                  only together with one of the three; not with -B, --ends-free, --affine2p or --wfa-adaptive\n"
            "\t    --affine2p-ends-free <pb,pe,tb,te> --affine2p under an ends-free span (the members as for --ends-free): only together with\n"
            "\t                                  --affine2p; not with -g, -B, --ends-free, --metric-ends-free, a metric or --wfa-adaptive\n"
+           "\t    --affine2p-wfa-adaptive <len,dist,steps> --affine2p under the wf-adaptive heuristic (the members as for --wfa-adaptive): only\n"
+           "\t                                  together with --affine2p; not with -B, --ends-free, --affine2p-ends-free or --wfa-adaptive\n"
            "[System]\n"
            "\t-t, --threads-per-block <int>     Accepted for compatibility (band width in banded mode)\n"
            "\t-w, --workers <int>               Accepted for compatibility\n"
@@ -97,7 +99,8 @@ int main(int argc, char** argv) {
         {"ends-free", required_argument, 0, 1001}, {"affine2p", required_argument, 0, 1002},
         {"wfa-adaptive", required_argument, 0, 1003}, {"edit", no_argument, 0, 1004}, {"indel", no_argument, 0, 1005},
         {"gap-linear", required_argument, 0, 1006}, {"metric-ends-free", required_argument, 0, 1007},
-        {"affine2p-ends-free", required_argument, 0, 1008}, {0, 0, 0, 0}};
+        {"affine2p-ends-free", required_argument, 0, 1008},
+        {"affine2p-wfa-adaptive", required_argument, 0, 1009}, {0, 0, 0, 0}};
     const char *seq_path = NULL, *q_path = NULL, *t_path = NULL, *out_path = NULL, *pen_str = NULL;
     long n_read = 0, max_distance = -1, batch_size = -1, band_arg = -2, tpb = -1, workers = -1;
     bool print_out = false, verbose = false, cigar = false, check = false, stage_times = false;
@@ -107,6 +110,7 @@ int main(int argc, char** argv) {
     const char* lin_str = NULL;
     const char* mspan_str = NULL;
     const char* p2span_str = NULL;
+    const char* p2ad_str = NULL;
     int n_metric = 0, metric = -1;
 
 
@@ -138,6 +142,7 @@ int main(int argc, char** argv) {
             case 1006: metric = WFAGPU_AMD_METRIC_GAP_LINEAR; lin_str = optarg; ++n_metric; break;
             case 1007: mspan_str = optarg; break;      /* (not in the reference: a metric under WFA2's ends-free alignment) */
             case 1008: p2span_str = optarg; break;     /* (not in the reference: gap_affine_2p under WFA2's ends-free alignment) */
+            case 1009: p2ad_str = optarg; break;       /* (not in the reference: gap_affine_2p under WFA2's wf-adaptive heuristic) */
             case 'h': usage(argv[0]); exit(0);
             default: break;      /* an option the tool does not know is skipped, like the reference's parser does (utils/arg_handler.c:97-140) */
         }
@@ -148,6 +153,29 @@ int main(int argc, char** argv) {
         return 1;
     }
 
+    /* --affine2p-wfa-adaptive: three integers, nothing behind them; only together with --affine2p, not together with -B, --ends-free,
+     * --affine2p-ends-free or --wfa-adaptive.  Checked first of all, before any device work and before another option could configure
+     * anything; the block of --affine2p below configures the two together. */
+    wfagpu_amd_wfadaptive_t p2ad = {0, 0, 0};
+    if (p2ad_str) {
+        char tail = 0;
+        if (sscanf(p2ad_str, "%d,%d,%d%c", &p2ad.min_wavefront_length, &p2ad.max_distance_threshold, &p2ad.steps_between_cutoffs, &tail) != 3 ||
+            p2ad.min_wavefront_length < 1 || p2ad.max_distance_threshold < 0 || p2ad.steps_between_cutoffs < 1) {
+            LOG_ERROR("--affine2p-wfa-adaptive takes three integers min_len>=1,max_dist>=0,steps>=1 (got \"%s\").", p2ad_str)
+            usage(argv[0]);
+            return 1;
+        }
+        if (!pen2_str) {
+            LOG_ERROR("--affine2p-wfa-adaptive is the heuristic of two-piece penalties: it goes together with --affine2p.")
+            usage(argv[0]);
+            return 1;
+        }
+        if (band_arg != -2 || span_str || p2span_str || wfad_str) {
+            LOG_ERROR("--affine2p-wfa-adaptive is a heuristic of the end-to-end two-piece search: it is not combined with -B, --ends-free, --affine2p-ends-free or --wfa-adaptive.")
+            usage(argv[0]);
+            return 1;
+        }
+    }
     /* --affine2p-ends-free: four non-negative integers, nothing behind them; only together with --affine2p, not together with -g, -B,
      * --ends-free, --metric-ends-free, a metric or --wfa-adaptive.  Checked first of all, before any device work and before
      * another option could configure anything; the block of --affine2p below configures the two together. */
@@ -230,6 +258,10 @@ int main(int argc, char** argv) {
             const wfagpu_amd_span_t p2span = {p2span4[0], p2span4[1], p2span4[2], p2span4[3]};
             if (wfagpu_amd_configure_affine2p_span(&pen2, &p2span) != 0) return 1;
             LOG_INFO("Ends-free under two-piece penalties: pattern begin/end free %d/%d, text begin/end free %d/%d.", p2span4[0], p2span4[1], p2span4[2], p2span4[3])
+        } else if (p2ad_str) {
+            if (wfagpu_amd_configure_affine2p_wfadaptive(&pen2, &p2ad) != 0) return 1;
+            LOG_INFO("WFA-Adaptive heuristic under two-piece penalties: min_wavefront_length=%d, max_distance_threshold=%d, steps_between_cutoffs=%d.",
+                     p2ad.min_wavefront_length, p2ad.max_distance_threshold, p2ad.steps_between_cutoffs)
         } else
         if (wfagpu_amd_configure_affine2p(&pen2) != 0) return 1;
         LOG_INFO("Two-piece gap-affine penalties: M=0, X=%d, O1=%d, E1=%d, O2=%d, E2=%d.", pen2.mismatch, pen2.gap_opening1, pen2.gap_extension1,

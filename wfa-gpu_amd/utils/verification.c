@@ -267,17 +267,16 @@ static long gap2p_cost(long n, int o1, int e1, int o2, int e2) {
     return a < b ? a : b;
 }
 
-bool check_affine2p_distance(const char* text, const char* pattern, size_t tlen, size_t plen,
-                             int distance, int x, int o1, int e1, int o2, int e2, const char* cigar) {
-    (void)text; (void)pattern; (void)tlen; (void)plen;
+/* the cost of a CIGAR under two pieces, every gap run priced as a whole by the cheaper piece; -1: not a CIGAR */
+static long affine2p_cigar_cost(int x, int o1, int e1, int o2, int e2, const char* cigar) {
     long cost = 0, gap = 0;     /* gap: bases of the I / D run that is open */
     char prev = 0;
     const char* c = cigar;
     while (*c) {
         long n; char op;
         c = next_item(c, &n, &op);
-        if (!c) return false;
-        if (op != 'M' && op != 'X' && op != 'I' && op != 'D') return false;
+        if (!c) return -1;
+        if (op != 'M' && op != 'X' && op != 'I' && op != 'D') return -1;
         /* a run ends where the operation changes: priced as a whole, by the cheaper piece */
         if (op != prev && gap) { cost += gap2p_cost(gap, o1, e1, o2, e2); gap = 0; }
         if (op == 'X') cost += n * x;
@@ -285,7 +284,20 @@ bool check_affine2p_distance(const char* text, const char* pattern, size_t tlen,
         prev = op;
     }
     if (gap) cost += gap2p_cost(gap, o1, e1, o2, e2);
-    return cost == distance;
+    return cost;
+}
+
+bool check_affine2p_distance(const char* text, const char* pattern, size_t tlen, size_t plen,
+                             int distance, int x, int o1, int e1, int o2, int e2, const char* cigar) {
+    (void)text; (void)pattern; (void)tlen; (void)plen;
+    return affine2p_cigar_cost(x, o1, e1, o2, e2, cigar) == distance;
+}
+
+bool check_affine2p_distance_heuristic(const char* text, const char* pattern, size_t tlen, size_t plen,
+                                       int distance, int x, int o1, int e1, int o2, int e2, const char* cigar) {
+    (void)text; (void)pattern; (void)tlen; (void)plen;
+    const long cost = affine2p_cigar_cost(x, o1, e1, o2, e2, cigar);
+    return cost >= 0 && cost <= distance;
 }
 
 int verification_cpu_score_2p(const char* pattern, const char* text, size_t plen, size_t tlen, int x, int o1, int e1, int o2, int e2) {

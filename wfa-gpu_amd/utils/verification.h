@@ -54,6 +54,12 @@ int verification_cpu_score_span(const char* pattern, const char* text, size_t pl
  * program of verification_cpu_score_scratch with five tables (M, and I / D once per piece). */
 bool check_affine2p_distance(const char* text, const char* pattern, size_t tlen, size_t plen,
                              int distance, int x, int o1, int e1, int o2, int e2, const char* cigar);
+/* Two pieces under the wf-adaptive heuristic (wfagpu_amd_configure_affine2p_wfadaptive): the score is that of the path WFA2 walked.
+ * Where the cut-off dropped the I2 / D2 cells of a long gap the path carries it on the first piece; printed, the gap is one run and
+ * the cheaper piece prices it lower.  So a CIGAR passes when it costs the score OR LESS (no valid CIGAR costs less than the optimum,
+ * which the score is judged against by verification_heuristic_verdict). */
+bool check_affine2p_distance_heuristic(const char* text, const char* pattern, size_t tlen, size_t plen,
+                                       int distance, int x, int o1, int e1, int o2, int e2, const char* cigar);
 int verification_cpu_score_2p_scratch(const char* pattern, const char* text, size_t plen, size_t tlen,
                                       int x, int o1, int e1, int o2, int e2, verification_scratch_t* scratch);
 int verification_cpu_score_2p(const char* pattern, const char* text, size_t plen, size_t tlen,
