@@ -3,10 +3,13 @@
 // BT, ASCII, LIN, EF and the kernel argument p are declared; the notes in front of wfa_short_kernel describe it.
 // EF (wfa_short_linef_kernel, short_kernel_linef.hip: the metrics; wfa_short_ef_kernel, short_kernel_ef_impl.h: gap-affine): under an
 // ends-free span -- a start row, an interval of end diagonals, the diagonal the alignment ended on to WfaAlignParams::ends.
-  static_assert(LIN ? (X >= 0 && X <= 8 && OE >= 1 && OE <= 4 && E == OE && (X > 0 || OE == 1)) : (X >= 1 && X <= 8 && OE >= 1 && OE <= 8 && E >= 1 && E <= OE && L >= 16), "history of eight scores");
-  constexpr int D = X > OE ? X : OE;
+// TP2 (wfa_short_2p_kernel, short_kernel_2p.hip): two-piece penalties, end to end -- OE / E are the first piece, OE2 / E2 the second; five
+// values per cell, their rings in registers (the notes in front of that kernel).  Every kernel declares TP2, OE2 and E2.
+  static_assert(TP2 ? (!LIN && !EF && X >= 1 && E >= 1 && OE >= E && E2 >= 1 && OE2 >= E2 && (L == 16 || L == 32)) : LIN ? (X >= 0 && X <= 8 && OE >= 1 && OE <= 4 && E == OE && (X > 0 || OE == 1)) : (X >= 1 && X <= 8 && OE >= 1 && OE <= 8 && E >= 1 && E <= OE && L >= 16), "history of eight scores");
+  // (TP2: max(X, OE, OE2) rounded up to a multiple of E and of E2 -- short2p_ring_depth --, so that the unrolled score loop finds every ring at a constant index)
+  constexpr int D = TP2 ? short2p_ring_depth(X, OE, E, OE2, E2) : (X > OE ? X : OE);
   constexpr int RL = L < 16 ? 16 : L;     // bytes of a row of origin bytes: whole 16-byte units
-  constexpr int DG = E == 1 ? 1 : D;      // depth of the I / D history
+  constexpr int DG = TP2 ? E : (E == 1 ? 1 : D);      // depth of the I / D history (TP2: of I1 / D1, exactly E scores back)
   extern __shared__ __attribute__((aligned(16))) uint32_t slds[];
   constexpr int G = 64 / L;
   const int lane = threadIdx.x & 63, grp = lane / L, j = lane % L;
@@ -181,11 +184,25 @@
     {
       long long worst = (long long)X * min(plen, tlen) + (kend ? OE + (long long)E * (abs(kend) - 1) : 0);
       if constexpr (LIN) worst = (long long)((X && X < 2 * OE) ? X : 2 * OE) * min(plen, tlen) + (long long)OE * abs(kend);
+      if constexpr (TP2) worst = (long long)X * min(plen, tlen) + wfa_gap2p(abs(kend), OE, E, OE2, E2);
       budget = (int)min((long long)budget, worst);
     }
     uint32_t status = WFA_ST_DONE;
     int wlo = 0;
-    if constexpr (EF && LIN) {
+    if constexpr (TP2) {
+      // (align_kernel.hip, TWOPIECE: a path that visits a diagonal t beyond both 0 and kend holds gaps of t + |kend| bases one way and t
+      // the other, g(t + |kend|) + g(t) <= S -- g the cheaper piece, subadditive; the largest such t by bisection, wfa_stray2p, once per
+      // alignment; feasible: g(|kend|) <= S)
+      if (active) {
+        const int ak = kend < 0 ? -kend : kend;
+        const bool feasible = wfa_gap2p(ak, OE, E, OE2, E2) <= (long long)budget;
+        const int t = feasible ? wfa_stray2p(budget, ak, OE, E, OE2, E2) : 0;
+        const int whi = min(max(0, kend) + t, tlen);
+        wlo = max(min(0, kend) - t, -plen);
+        if (!feasible) status = WFA_ST_SCORE;
+        else if (whi - wlo + 1 > L || pwords > cap || twords > cap) status = WFA_ST_BAND;
+      }
+    } else if constexpr (EF && LIN) {
       // (align_kernel.hip, LINEAR && ENDSFREE: the hull of the start diagonals [-pbf, tbf] and the end diagonals [kend - tef, kend + pef],
       // beyond it (gb - what the two intervals leave between them) / 2 -- quotients of non-negative numerators only)
       if (active) {
@@ -302,6 +319,11 @@
     int ig[DG], dg[DG];                                     // E == 1: I and D of the last score; else of the scores with (s % D) == index (LIN: unused)
 #pragma unroll
     for (int i = 0; i < DG; ++i) { ig[i] = S_NULL; dg[i] = S_NULL; }
+    int ig2[TP2 ? E2 : 1], dg2[TP2 ? E2 : 1];               // (TP2) I2 and D2 of the scores with (s % E2) == index
+    if constexpr (TP2) {
+#pragma unroll
+      for (int i = 0; i < E2; ++i) { ig2[i] = S_NULL; dg2[i] = S_NULL; }
+    }
     {
       bool mine = run && k == 0;
       int h_start = 0;
@@ -393,13 +415,53 @@
         else if (s >= budget) { fin = true; status = WFA_ST_SCORE; }
       }
     };
+    // TP2, one score (the cells of align/loop_careful_2p.inc: seven sources, five values): reads M[s - X], M[s - OE], M[s - OE2] by value
+    // and I1 / D1[s - E], I2 / D2[s - E2] from the ring slots it then writes.  The SOURCE lane takes the max of opening and extension,
+    // so each component crosses to its neighbour once: four lane shifts per score instead of eight; with CIGARs the four "extension won
+    // or tied" flags (wavefront_compute_affine2p.c:173,191,214,232) cross as two more -- the I flags upwards, the D flags downwards.
+    // Lanes without a neighbour get NULL (flags: none -- their gap values are NULL, nobody asks where they came from).
+    auto step_2p = [&](int& m_out, int& i1, int& d1, int& i2, int& d2, const int m_x, const int m_o1, const int m_o2) {
+      if constexpr (TP2) {
+        ++s;
+        const int ins1 = short2p_from_below<L>(max(m_o1, i1), j) + 1, ins2 = short2p_from_below<L>(max(m_o2, i2), j) + 1;
+        const int del1 = short2p_from_above<L>(max(m_o1, d1), j), del2 = short2p_from_above<L>(max(m_o2, d2), j);
+        uint32_t ext = 0;
+        if constexpr (BT) {
+          const int f_i = (i1 >= m_o1 ? (int)BT2_I1_EXT : 0) | (i2 >= m_o2 ? (int)BT2_I2_EXT : 0);
+          const int f_d = (d1 >= m_o1 ? (int)BT2_D1_EXT : 0) | (d2 >= m_o2 ? (int)BT2_D2_EXT : 0);
+          ext = (uint32_t)(short2p_from_below<L, 0>(f_i, j) | short2p_from_above<L, 0>(f_d, j));
+        }
+        const int mis = m_x + 1;
+        // !(h > tlen || v > plen), unsigned so that NULLs fail too (wavefront_compute_affine2p.c:46-106); a value past an end is NULL at
+        // once (DESIGN.md section 4.16: no cell of an optimal path reads one)
+        i1 = ((uint32_t)(ins1 - h_lo) <= h_span) ? ins1 : S_NULL;
+        i2 = ((uint32_t)(ins2 - h_lo) <= h_span) ? ins2 : S_NULL;
+        d1 = ((uint32_t)(del1 - h_lo) <= h_span) ? del1 : S_NULL;
+        d2 = ((uint32_t)(del2 - h_lo) <= h_span) ? del2 : S_NULL;
+        const int mv = max(max(max(d2, d1), max(i2, i1)), mis);
+        if constexpr (BT) {
+          // M on equal offsets: mismatch, D2, D1, I2, I1 (wavefront_compute_affine2p.c:251-270, wavefront_backtrace.c:49-59)
+          if (!fin) lrows[s * RL] = (uint8_t)(ext | ((mis == mv) ? BT2_M_X : (d2 == mv) ? BT2_M_D2 : (d1 == mv) ? BT2_M_D1 : (i2 == mv) ? BT2_M_I2 : BT2_M_I1));
+        }
+        const bool ok = !fin & ((uint32_t)(mv - h_lo) <= h_span);
+        const int h = extend(mv, ok);
+        m_out = ok ? h : S_NULL;
+        const bool hit = ok && k == kend && h >= tlen;
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(hit);
+        if (!fin) {
+          if ((bal & grp_mask) != 0ull) { fin = true; score = s; }
+          else if (s >= budget) { fin = true; status = WFA_ST_SCORE; }
+        }
+      }
+    };
     // s % D runs 1, 2, .., D - 1, 0, 1, ..: M[s - X] sits in register (s - X) % D, M[s - OE] in (s - OE) % D
     bool more = __builtin_amdgcn_ballot_w64(!fin) != 0ull;
     while (more) {
 #pragma unroll
       for (int r = 1; r <= D; ++r) {
         if (more) {
-          if constexpr (LIN) step_lin(m[r % D], m[(r - X + D) % D], m[(r - OE + D) % D]);
+          if constexpr (TP2) step_2p(m[r % D], ig[r % E], dg[r % E], ig2[r % E2], dg2[r % E2], m[(r - X + D) % D], m[(r - OE + D) % D], m[(r - OE2 + D) % D]);
+          else if constexpr (LIN) step_lin(m[r % D], m[(r - X + D) % D], m[(r - OE + D) % D]);
           else if constexpr (E == 1) step(m[r % D], ig[0], dg[0], m[(r - X + D) % D], m[(r - OE + D) % D], ig[0], dg[0]);
           else step(m[r % D], ig[r % D], dg[r % D], m[(r - X + D) % D], m[(r - OE + D) % D], ig[(r - E + D) % D], dg[(r - E + D) % D]);
           more = __builtin_amdgcn_ballot_w64(!fin) != 0ull;

@@ -37,7 +37,8 @@ namespace {
 template <int L, int X, int OE, int E, bool BT, bool ASCII>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8)))
 wfa_short_ef_kernel(const WfaAlignParams p) {
-  constexpr bool LIN = false, EF = true;
+  constexpr bool LIN = false, EF = true, TP2 = false;
+  constexpr int OE2 = OE, E2 = E;      // (two pieces only: short_kernel_2p.hip)
 #include "short_kernel_body.inc"
 }
 

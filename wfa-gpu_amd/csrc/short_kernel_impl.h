@@ -27,6 +27,27 @@ template <int L> __device__ __forceinline__ int from_above(int v, int j) {
   else { const int r = __shfl_down(v, 1, L); return j == L - 1 ? S_NULL : r; }
 }
 
+// Two pieces (TP2, short_kernel_2p.hip).  Depth of the M ring: max(x, o1 + e1, o2 + e2) scores back, rounded up to a multiple of e1 and
+// of e2 -- the score loop is unrolled once around the M ring, and the I1 / D1 (I2 / D2) rings of e1 (e2) registers must come round to
+// their first slot with it, or their indices would not be constants.
+constexpr int short2p_ring_depth(int x, int oe1, int e1, int oe2, int e2) {
+  int d = x > oe1 ? x : oe1;
+  if (oe2 > d) d = oe2;
+  while (d % e1 || d % e2) ++d;
+  return d;
+}
+// Its neighbour shifts: as above for 16 lanes; for 32 a DPP wave shift by one lane (the wavefront holds two groups: lane 0 / 31 of a
+// group takes NONE instead of what crossed the seam) where from_below / from_above go through the LDS crossbar (ds_bpermute_b32, an
+// address register and a round trip per shift: six shifts per score here).
+template <int L, int NONE = S_NULL> __device__ __forceinline__ int short2p_from_below(int v, int j) {
+  if constexpr (L == 16) return __builtin_amdgcn_update_dpp(NONE, v, 0x111 /* row_shr:1 */, 0xF, 0xF, false);
+  else { const int r = __builtin_amdgcn_update_dpp(NONE, v, 0x138 /* wave_shr:1 */, 0xF, 0xF, false); return j == 0 ? NONE : r; }
+}
+template <int L, int NONE = S_NULL> __device__ __forceinline__ int short2p_from_above(int v, int j) {
+  if constexpr (L == 16) return __builtin_amdgcn_update_dpp(NONE, v, 0x101 /* row_shl:1 */, 0xF, 0xF, false);
+  else { const int r = __builtin_amdgcn_update_dpp(NONE, v, 0x130 /* wave_shl:1 */, 0xF, 0xF, false); return j == L - 1 ? NONE : r; }
+}
+
 // X = mismatch, OE = gap open + extend, E = gap extend.  L lanes per alignment.  The history a cell reads -- M of the last
 // D = max(X, OE) scores -- is a ring of D registers per lane; the score loop is unrolled D times so that every ring index is a
 // compile-time constant (round 3 had the two instantiations of the benchmark penalties; round 4 every set with e == 1 and
@@ -66,7 +87,8 @@ template <int L> __device__ __forceinline__ int from_above(int v, int j) {
 template <int L, int X, int OE, int E, bool BT, bool ASCII>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((BT && E == 1) ? (ASCII ? 5 : 6) : 1, 8)))
 wfa_short_kernel(const WfaAlignParams p) {
-  constexpr bool LIN = false, EF = false;
+  constexpr bool LIN = false, EF = false, TP2 = false;
+  constexpr int OE2 = OE, E2 = E;      // (two pieces only: short_kernel_2p.hip)
 #include "short_kernel_body.inc"
 }
 

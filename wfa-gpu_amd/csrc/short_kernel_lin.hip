@@ -18,8 +18,8 @@ namespace {
 template <int L, int X, int GAP, bool BT, bool ASCII>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8)))
 wfa_short_lin_kernel(const WfaAlignParams p) {
-  constexpr bool LIN = true, EF = false;
-  constexpr int OE = GAP, E = GAP;      // (every gap base costs g, nothing opens)
+  constexpr bool LIN = true, EF = false, TP2 = false;
+  constexpr int OE = GAP, E = GAP, OE2 = GAP, E2 = GAP;      // (every gap base costs g, nothing opens; OE2 / E2: two pieces only)
 #include "short_kernel_body.inc"
 }
 

@@ -394,10 +394,17 @@ void wfa_prime_short_ef(hipStream_t stream);
 const WfaShortEntry* wfa_short_ef_entry_e2(int ascii, int bt, int li, int idx);
 const WfaShortEntry* wfa_short_ef_entry_e3(int ascii, int bt, int li, int idx);
 const WfaShortEntry* wfa_short_ef_entry_e4(int ascii, int bt, int li, int idx);
+// Tier 5 under two-piece penalties, end to end (short_kernel_2p.hip: a code object of its own, loaded only by two-piece calls whose
+// window bound -- window_width_2p -- fits a group): lanes = 16 or 32, five rings in registers, BT2_* origin bytes.  The penalty sets of
+// ONE table, after the common-factor reduction (oe1 = o1 + e1, oe2 = o2 + e2); wfa_short_lds_bytes and wfa_short_bt_slot_units serve it too.
+bool wfa_short_2p_supported(int x, int oe1, int e1, int oe2, int e2);
+void wfa_launch_short_2p(const WfaAlignParams& p, int lanes, bool with_bt, int grid, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+int wfa_short_2p_max_blocks_per_cu(const WfaAlignParams& p, int lanes, bool with_bt);
+void wfa_prime_short_2p(hipStream_t stream);
 // Which of the optional code objects -- the ones only some callers load -- this process has entered: every host function that launches,
 // queries or primes a kernel of such a unit says so (the runtime loads a code object at the first of these).  Process-wide, never
 // cleared; wfagpu_amd_debug_code_objects() (wfa_host.hip) hands the bits out, tests check "never loaded" with them.
-enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u, WFA_UNIT_ALIGN_AD = 8u, WFA_UNIT_ALIGN_LIN = 16u, WFA_UNIT_TRACE_LIN = 32u, WFA_UNIT_ALIGN_LINEF = 64u, WFA_UNIT_SHORT_LIN = 128u, WFA_UNIT_SHORT_LINEF = 256u, WFA_UNIT_SHORT_EF = 512u, WFA_UNIT_ALIGN_2PEF = 1024u, WFA_UNIT_ALIGN_2PAD = 2048u };
+enum : unsigned { WFA_UNIT_ALIGN_EF = 1u, WFA_UNIT_ALIGN_2P = 2u, WFA_UNIT_TRACE_2P = 4u, WFA_UNIT_ALIGN_AD = 8u, WFA_UNIT_ALIGN_LIN = 16u, WFA_UNIT_TRACE_LIN = 32u, WFA_UNIT_ALIGN_LINEF = 64u, WFA_UNIT_SHORT_LIN = 128u, WFA_UNIT_SHORT_LINEF = 256u, WFA_UNIT_SHORT_EF = 512u, WFA_UNIT_ALIGN_2PEF = 1024u, WFA_UNIT_ALIGN_2PAD = 2048u, WFA_UNIT_SHORT_2P = 4096u };
 void wfa_unit_entered(unsigned unit);
 // Code-object priming: one empty launch per kernel translation unit (see the definitions).
 void wfa_prime_pack(hipStream_t stream);

@@ -510,8 +510,9 @@ int wfagpu_amd_prime(wfagpu_amd_ctx_t* c) {
   wfa_prime_pack(c->stream);
   wfa_prime_short(c->stream);
   if (wfa_configured_span(nullptr)) { wfa_prime_align_ef(c->stream); wfa_prime_short_ef(c->stream); }      // (the ends-free kernels: only callers under a span load them)
-  // (the two-piece kernels: only callers under such penalties -- the ends-free ones where they were configured with a span)
-  if (wfa_configured_affine2p(nullptr)) { if (wfa_configured_affine2p_span(nullptr)) wfa_prime_align_2pef(c->stream); else wfa_prime_align_2p(c->stream); wfa_prime_trace_2p(c->stream); }
+  // (the two-piece kernels: only callers under such penalties -- the ends-free ones where they were configured with a span, else the
+  // end-to-end ones with their short-read tier)
+  if (wfa_configured_affine2p(nullptr)) { if (wfa_configured_affine2p_span(nullptr)) wfa_prime_align_2pef(c->stream); else { wfa_prime_align_2p(c->stream); wfa_prime_short_2p(c->stream); } wfa_prime_trace_2p(c->stream); }
   if (wfa_configured_wfadaptive(nullptr)) wfa_prime_align_ad(c->stream);      // (the wf-adaptive kernels: only callers under the heuristic)
   // (the heuristic under two pieces -- wfagpu_amd_configure_affine2p_wfadaptive --: its wavefront kernels and the two-piece backtrace)
   if (wfa_configured_affine2p_wfadaptive(nullptr)) { wfa_prime_align_2pad(c->stream); wfa_prime_trace_2p(c->stream); }
@@ -624,7 +625,7 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
   // Ends-free (p.ends): the window is the end-to-end one around the hull of the start and end diagonals -- wider by at most the
   // free bases (clamped to the sequences).  A bound for the longest pair, not an exact figure: a pair whose own window is wider
   // comes back as a BAND failure and is escalated like any other.  Tiers 0, 1, 2 and 3, and tier 5 where the bound fits a group (below).
-  // Two pieces (p.e2 > 0): tiers 0, 1, 2 and 3 of the exact search, like ends-free.
+  // Two pieces (p.e2 > 0): tiers 0, 1, 2 and 3 of the exact search, like ends-free, and -- end to end -- tier 5 where the bound fits a group (below).
   // Two pieces under a span (p.e2 > 0 and p.ends: align_kernel_2pef.hip): rings with the two-piece row counts, window_width_2p widened by
   // the free bases like the gap-affine span -- the kernel's window is the stray of the budget on either side of the hull of the start
   // and end diagonals, and the hull is at most the free bases wider than [min(0, kend), max(0, kend)].
@@ -705,6 +706,23 @@ bool plan_tier(const wfagpu_amd_ctx* c, WfaAlignParams& p, int max_score, unsign
     const size_t lds = wfa_short_lds_bytes(p, lanes, bt);
     if (lds <= 40u << 10) {
       const int nb = std::min(32, wfa_short_ef_max_blocks_per_cu(p, lanes, bt));
+      if (nb >= 1) {
+        *out = {5, width, max_score, lds, nb, lanes};
+        return true;
+      }
+    }
+  }
+  // Two pieces, end to end (short_kernel_2p.hip: 16 or 32 lanes, M, I1, D1, I2 and D2 rings in registers): width is window_width_2p's
+  // bound, R(S) + 3 diagonals, which holds every pair's own window; the smallest group with a lane to spare.  No 64-lane groups (the
+  // gap-affine end-to-end tier has none either); penalty sets outside wfa_short_2p_supported's table stay on the one-wave tiers.
+  // (No budgets are tuned under two pieces: the tier is taken when the caller's max_error makes the bound fit.)
+  if (tp2 && !ef && !ad && !lin && !raw && !(p.ascii && !c->short_ascii_ok) && c->tuning.min_tier == 0 && !(bt && c->tuning.no_short_cigar) && width + 1 <= 32 && max_score <= 30000 && wfa_short_2p_supported(p.x, p.oe, p.e, p.oe2, p.e2)) {
+    // (tuning.waves_per_simd 32: at least that many lanes -- the A/B of the group widths, profiles/r19)
+    const int lanes = (width + 1 <= 16 && c->tuning.waves_per_simd != 32) ? 16 : 32;
+    p.rs = 0;
+    const size_t lds = wfa_short_lds_bytes(p, lanes, bt);
+    if (lds <= 40u << 10) {
+      const int nb = std::min(32, wfa_short_2p_max_blocks_per_cu(p, lanes, bt));
       if (nb >= 1) {
         *out = {5, width, max_score, lds, nb, lanes};
         return true;
@@ -1027,7 +1045,10 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
   // max_error says whether the tier will be taken -- plan_tier's rule)
   // (under a span: plan_tier's bound -- S / g + 1, gap-affine (S - o) / e + 1, plus the clamped free bases -- within 64 lanes)
   const long long ef_free = ef ? std::min<long long>(span->pattern_begin_free, batch_max_len) + std::min<long long>(span->pattern_end_free, batch_max_len) + std::min<long long>(span->text_begin_free, batch_max_len) + std::min<long long>(span->text_end_free, batch_max_len) : 0;
-  const bool short_fuses = !tp2 && !ad && (lin ? (wfa_short_lin_supported(ap.x, pen.e) && (ef ? std::min<long long>(2ll * batch_max_len + 1, max_error / pen.e + 1 + ef_free) + 1 <= 64 : max_error / pen.e + 2 <= 32)) : (wfa_short_supported(pen.x, oe, pen.e) && (!ef || std::min<long long>(2ll * batch_max_len + 1, window_width(max_error, pen.o, pen.e, batch_max_len) + ef_free) + 1 <= 64))) && !c->tuning.min_tier && !(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
+  // (two pieces, end to end: plan_tier's bound -- window_width_2p, R(S) + 3 -- within 32 lanes, for a set of the tier's table)
+  const bool short_fuses_2p = tp2 && !ef && !ad && wfa_short_2p_supported(pen.x, oe, pen.e, o2 + e2, e2) && max_error <= 30000 &&
+                              std::min<long long>(2ll * batch_max_len + 1, wfa_reach2p(max_error, oe, pen.e, o2 + e2, e2) + 3) + 1 <= 32;
+  const bool short_fuses = (short_fuses_2p || (!tp2 && !ad && (lin ?(wfa_short_lin_supported(ap.x, pen.e) && (ef ? std::min<long long>(2ll * batch_max_len + 1, max_error / pen.e + 1 + ef_free) + 1 <= 64 : max_error / pen.e + 2 <= 32)) : (wfa_short_supported(pen.x, oe, pen.e) && (!ef || std::min<long long>(2ll * batch_max_len + 1, window_width(max_error, pen.o, pen.e, batch_max_len) + ef_free) + 1 <= 64))))) && !c->tuning.min_tier &&!(compute_cigar && c->tuning.no_short_cigar) && c->short_ascii_ok;
   const bool fused_pack = !prepacked && (b->max_seq_len >= 512u || short_fuses) && !c->tuning.no_fused_pack;
   // Every status starts as PENDING = 0: written by the pack kernel where it runs (it visits every pair anyway), by a memset (a
   // launch of its own, ~5 us + a gap) where it does not -- queued by whoever reads the array first (ensure_status), and not at all
@@ -1279,6 +1300,7 @@ static int align_device_impl(wfagpu_amd_ctx_t* c, const wfagpu_amd_batch_t* b,
           if (lin && ef) wfa_launch_short_linef(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
           else if (ef) wfa_launch_short_ef(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
           else if (lin) wfa_launch_short_lin(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
+          else if (tp2) wfa_launch_short_2p(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
           else wfa_launch_short(ap, tp.wpe, cigar_now, grid, st, L.e0, L.e1);
           if (solo && !cigar_now) call_end = L.e1;      // (the chain's last kernel)
           // (with CIGARs the launch owns n_cur slots above the bump pointer: move it past them for whatever allocates next)
