@@ -1,18 +1,21 @@
 """What two-piece gap-affine alignment costs: 1 kbp reads at 5 % error under (4,6,2,24,1), against the same pairs under gap-affine
-(4,6,2) held to the careful loop (tuning.careful_only: the like-for-like baseline -- the two-piece kernels have no lean loop) and under
-gap-affine as shipped; score-only and with CIGARs.  Prints the tier of the main launch and the LDS of a workgroup (one ring).
+(4,6,2) held to the careful loop (tuning.careful_only: the like-for-like baseline) and under gap-affine as shipped, and against the
+two-piece call itself held to the careful loop (careful_only: what the two-piece kernels ran before their lean loop, loop_lean_2p.inc);
+score-only and with CIGARs.  Prints the tier of the main launch and the LDS of a workgroup (one ring).
 A library without the two-piece entry point (the parent commit) runs the gap-affine legs only.
-   scratch/affine2p_probe.py [pairs] [repeats]"""
+   scratch/affine2p_probe.py [pairs] [repeats] [length] [max_error] [2p]      (2p: the two-piece legs only)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "wfa-gpu_amd", "bindings")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch, wfagpu
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 100_000
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
-pen, pen2, me = (4, 6, 2), (4, 6, 2, 24, 1), 600
+length = int(sys.argv[3]) if len(sys.argv) > 3 else 1000
+pen, pen2, me = (4, 6, 2), (4, 6, 2, 24, 1), int(sys.argv[4]) if len(sys.argv) > 4 else 600
+only_2p = len(sys.argv) > 5 and sys.argv[5] == "2p"
 have_2p = hasattr(wfagpu.load(), "wfagpu_amd_align_device_2p")
-buf, meta = wfagpu.generate_pairs(n, 1000, 0.05, seed=4242, nthreads=16)
-print(f"{n} pairs of 1 kbp at 5 %; two-piece entry point: {have_2p}", flush=True)
+buf, meta = wfagpu.generate_pairs(n, length, 0.05, seed=4242, nthreads=16)
+print(f"{n} pairs of {length} bp at 5 %, max_error {me}; two-piece entry point: {have_2p}", flush=True)
 
 
 def leg(name, cigar, affine2p=None, **tuning):
@@ -38,6 +41,9 @@ for cigar in (False, True):
     tag = "cigar" if cigar else "score"
     if have_2p:
         leg(f"two pieces (4,6,2,24,1) [{tag}]", cigar, affine2p=pen2)
+        leg(f"two pieces (4,6,2,24,1) careful_only [{tag}]", cigar, affine2p=pen2, careful_only=1)
+    if only_2p:
+        continue
     leg(f"gap-affine (4,6,2) careful_only no_auto_budget [{tag}]", cigar, careful_only=1, no_auto_budget=1)
     leg(f"gap-affine (4,6,2) careful_only [{tag}]", cigar, careful_only=1)
     leg(f"gap-affine (4,6,2) as shipped [{tag}]", cigar)

@@ -65,6 +65,7 @@
 //   align/loop_lean_hbm.inc   lean score loop of the tiers whose ring lives in HBM
 //   align/loop_careful.inc    the careful score step (WFA2 to the letter)
 //   align/loop_careful_2p.inc the careful score step of the two-piece instantiations
+//   align/cells_hot_2p.inc, align/loop_lean_2p.inc   the lean cells and the lean score loop of the exact end-to-end two-piece instantiations (LDS tiers)
 //   align/loop_careful_ad.inc the careful score step of the wf-adaptive instantiations (WFA2's heuristic cut-off)
 //   align/loop_careful_2pad.inc the careful score step of the wf-adaptive instantiations under two-piece penalties
 //   align/loop_careful_lin.inc the careful score step of the one-component instantiations (edit, indel, gap-linear), cells included
@@ -759,6 +760,7 @@ wfa_align_kernel(const WfaAlignParams p) {
       if constexpr (BT && !TILED) { if (status == WFA_ST_DONE) tab_set(0, row_s, 0); }
       #include "align/cells_generic.inc"
       #include "align/cells_hot.inc"
+      #include "align/cells_hot_2p.inc"
       #include "align/band_window.inc"
       // Limits of the last score (the lean path derives the next ones from them alone).
       int last_lo = 0, last_hi = 0;
@@ -766,13 +768,15 @@ wfa_align_kernel(const WfaAlignParams p) {
       // I or D value run past a sequence end (every such value has a predecessor chain that starts at an M cell sitting
       // on the border), and only such a cell can be the final one.  Until then the lean path needs neither the
       // per-cell overrun tests nor the per-score termination read.
-      // (ENDSFREE: the careful loop only -- a row of score 0 that starts on the borders has touched them)
-      bool touched_ever = ENDSFREE || TWOPIECE || touched_at_0 || cold_params()->no_lean != 0;    // (WFAGPU_NO_LEAN: the lean path is never entered)
+      // (ENDSFREE: the careful loop only -- a row of score 0 that starts on the borders has touched them; TWOPIECE: the lean loop of
+      // loop_lean_2p.inc serves the exact end-to-end instantiations of the 16-bit LDS tiers, the others keep the careful loop only)
+      bool touched_ever = ENDSFREE || (TWOPIECE && (ADAPTIVE || !HOT)) || touched_at_0 || cold_params()->no_lean != 0;    // (WFAGPU_NO_LEAN: the lean path is never entered)
       // ---- score loop ----------------------------------------------------------------------------
       if (!done && status == WFA_ST_DONE) for (;;) {
         if constexpr (TWOPIECE && ADAPTIVE) {
           #include "align/loop_careful_2pad.inc"
         } else if constexpr (TWOPIECE) {
+          #include "align/loop_lean_2p.inc"
           #include "align/loop_careful_2p.inc"
         } else if constexpr (ADAPTIVE) {
           #include "align/loop_careful_ad.inc"
